@@ -10,7 +10,9 @@ all-reduce of the G/D gradients.  ``--gpus N`` with N > 1 and no torchrun enviro
 starts the N rank processes itself (a child ``torch.distributed.run``, launched before
 this process touches the GPU) and relays rank 0's line.
 
-Prints ONE JSON line on rank 0 (the driver contract), with:
+A plain run sets up, warms up, times ``--steps`` steps and prints ONE JSON line on rank 0 (the driver contract):
+images/s as ``value``, ``ms_per_step`` and the whole step's MFMA fraction.  ``--dump-outputs DIR`` also writes what
+the last timed step computed (dump_outputs).  ``--full`` adds to the line, from runs of their own after the timed steps:
   roofline      the dominant kernel by summed device time over every conv-family launch of
                 one train step (HIP events bracketing each MAIN kernel, not the reductions
                 enqueued after it), its algorithmic TFLOP/s vs the bf16/fp32 MFMA peak, its HBM
@@ -71,8 +73,14 @@ def parse():
     ap.add_argument("--graph", action="store_true", help="replay the step captured as one HIP graph "
                     "(STCGAN.capture; the same kernels, bit-identical results) instead of eager steps")
     ap.add_argument("--no-lanes", action="store_true", help="discriminators on the main stream (no side lanes; A/B)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the parity / other-config measurements")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure the roofline (per-kernel "
+                    "HIP events), the G2 parity and the other configs, and the CPU baseline; a plain run times the "
+                    "steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed "
+                    "(its loss scalars and a seeded sample of every network's updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the parity / other-config "
+                    "measurements")
     ap.add_argument("--cpu-batch", type=int, default=32, help="batch of the timed CPU train step (C3: 32)")
     return ap.parse_args()
 
@@ -177,6 +185,33 @@ def make_trainer(ngf, dtype, local):
                               dtype=dtype, load_weights_g1=None, load_weights_g2=None,
                               load_weights_d1=None, load_weights_d2=None)
     return STCGAN(a)
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept per network by --dump-outputs (4 MB of float32 each)
+
+
+def dump_outputs(path, tr, vals):
+    """--dump-outputs: what the last timed step handed its caller, as path/<name>.npy (float32).  ``vals`` are the
+    loss scalars train_step returned (None for a graph replay, which returns nothing); the step's other result is
+    the trainer's state, so of each network the parameters and floating-point buffers (BatchNorm running statistics)
+    after the update are written too, flattened in registration order and reduced to DUMP_SAMPLE elements at fixed,
+    seeded positions.  Seeds, inputs and positions depend on the arguments alone: two builds run with the same
+    arguments can be compared file by file."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for k, v in (vals or {}).items():
+        np.save(os.path.join(path, f"loss_{k}.npy"), v.detach().float().cpu().numpy().reshape(1))
+    for i, name in enumerate(("G1", "G2", "D1", "D2")):
+        net = getattr(tr, name)
+        parts = list(net.parameters()) + [b for b in net.buffers() if b.is_floating_point()]
+        flat = torch.cat([t.detach().float().reshape(-1) for t in parts])
+        if flat.numel() > DUMP_SAMPLE:
+            gen = torch.Generator()
+            gen.manual_seed(4321 + i)
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=gen).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(path, f"state_{name}.npy"), flat.cpu().numpy())
 
 
 def alg_bytes(name, desc):
@@ -496,8 +531,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    vals = None
     for _ in range(args.steps):
-        step()
+        vals = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -510,7 +546,12 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
 
-    roofline = roofline_of_step(tr, x, m, y, args, B, s)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, vals)
+
+    # a plain run stops here: the per-kernel roofline, the parity and other-config measurements and the CPU
+    # baseline take runs of their own and are made with --full only
+    roofline = roofline_of_step(tr, x, m, y, args, B, s) if args.full else {}
     step_gf = (STEP_GFLOP_PER_IMG - SKIPPED_LOGITS_GFLOP_PER_IMG) * B
     step_tf = step_gf / (ms_per_step * 1e-3) / 1e3
     roofline["whole_step"] = {"gflop": round(step_gf, 1), "ms": round(ms_per_step, 3),
@@ -523,12 +564,12 @@ def main():
         dist.barrier()
 
     extras, cpu = {}, None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         del tr
         torch.cuda.empty_cache()
         extras["parity"] = g2_parity(args, local)
         extras["configs"] = other_configs(args, local)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
     if rank == 0:
         out = {"metric": METRIC, "value": round(value, 3), "unit": "images/s", "n_gpus": world,

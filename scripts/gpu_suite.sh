@@ -10,6 +10,6 @@ echo "suite rc=$rc" >> $O/suite.log
 tail -3 $O/suite.log
 [ $rc -eq 0 ] || exit $rc
 if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 400 python -u bench.py --no-cpu-baseline > $O/bench.log 2>&1 || exit 1
+  timeout -k 10 400 python -u bench.py --full --no-cpu-baseline > $O/bench.log 2>&1 || exit 1
   tail -1 $O/bench.log | cut -c1-600
 fi

@@ -3,7 +3,7 @@
 # and two PMC passes (FETCH_SIZE, WRITE_SIZE) for per-launch HBM traffic.  Output: gpurun_out/$1/
 set -o pipefail
 OUT=gpurun_out/${1:-r01_bf16}
-ARGS=${BENCH_ARGS:---steps 5 --warmup 2 --no-cpu-baseline}
+ARGS=${BENCH_ARGS:---full --steps 5 --warmup 2 --no-cpu-baseline}
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 300 python bench.py $ARGS > $OUT/bench.log 2>&1 || exit $?

@@ -18,6 +18,8 @@
  *   stc_chan_stats / stc_bn_finalize               BatchNorm2d train/eval forward, STCGAN/networks.py:107,109,170,179
  *   stc_bn_bwd_reduce / stc_bn_bwd_apply            BatchNorm2d backward fused with LeakyReLU/ReLU backward
  *                    (with mean == NULL: LeakyReLU(0.2)/ReLU backward alone, networks.py:106,108,158)
+ *   stc_bn_apply_drop / stc_bn_bwd_*_drop / stc_dropout_*  nn.Dropout after the up-norm (use_dropout=True),
+ *                    STCGAN/networks.py UnetSkipConnectionBlock: counter-based Philox masks, nothing stored
  *   stc_tanh_bias_bwd Tanh backward + outermost ConvT bias grad (networks.py:112-116)
  *   stc_gather_nchw / stc_scatter_nchw              torch.cat input concat (stcgan.py:219-227,269-272) / its backward
  *   stc_loss_fwd / stc_loss_bwd                     DataLoss (L1) and AdversarialLoss (MSE / BCE-with-logits), loss.py:14-26,59-86
@@ -287,6 +289,56 @@ int stc_bn_bwd_apply(int dtype, int B, stc_view x, int C,
                      stc_view g1, float slope1, stc_view g2, float slope2,
                      const float* part2, int nchunks,
                      stc_view dx, float* dgamma, float* dbeta, void* stream);
+
+/* ---- dropout of the U-Net generator (use_dropout=True) ----------------------------------------------
+ * The reference appends nn.Dropout(0.5) after the up-norm of the num_downs - 5 blocks above the innermost one
+ * (STCGAN/networks.py UnetSkipConnectionBlock; src/models/stcgan_g.py:113-114).  Train mode only:
+ *   d = n * keep * 1/(1-p)        n = the BatchNorm output, over the full ConvT extent (before an odd level's crop)
+ * and, with g the gradient reaching the consumer's ReLU, the gradient reaching n is g * [n > 0] * keep * 1/(1-p).
+ * No mask is stored; keep is a pure function, evaluated by one device function (csrc/philox.hpp) in every kernel:
+ *   Philox4x32-10 (Random123 constants; counter = key = 0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8)
+ *   key     = the 64-bit seed (lo, hi)
+ *   counter = (idx >> 2, level, offset lo, offset hi), the element using output word idx & 3
+ *             idx   = the element's NHWC linear index over the full extent (B, H, W, C), idx < 2^34
+ *             level = the block whose up-norm output is dropped (0 = outermost)
+ *   keep <=> word >= floor(p * 2^32) (unsigned);  scale = 1/(1-p) in fp32, applied to the fp32 BatchNorm output
+ *   before the rounding to the storage dtype.
+ * state: device int64 {seed, offset} of ONE call.  stc_dropout_next makes that copy from a generator's running
+ * {seed, offset} and increments the running offset -- one tiny launch per train-mode forward, so that nothing
+ * host-side is baked into a launch (a replayed HIP graph draws a fresh mask) and the backward of a call recomputes
+ * the masks of its own forward.                                                                           */
+typedef struct {
+  const int64_t* state;  /* device {seed, offset} of this call                          */
+  double p;              /* drop probability, 0 <= p < 1                                */
+  int32_t level;
+  int32_t H, W;          /* the full extent the logical index runs over                 */
+  int32_t pad_;
+} stc_dropout;
+/* call_state = {seed, offset}; state.offset += 1 */
+int stc_dropout_next(int64_t* state, int64_t* call_state, void* stream);
+/* out[B][H][W][C] (uint8) = keep (1) / drop (0) over the full extent; C % 4 == 0 */
+int stc_dropout_mask(const stc_dropout* drop, int B, int C, uint8_t* out, void* stream);
+/* stc_bn_apply with the dropout between the affine and the activation(s): y = act(n * keep/(1-p), slope); x's extent
+ * may be a crop (rows / columns from 0) of the full extent.  stc_conv_bn_fwd_drop: stc_conv_bn_fwd with this apply. */
+int stc_bn_apply_drop(int dtype, int B, stc_view x, int C, const float* scale, const float* shift,
+                      stc_view y1, float slope1, stc_view y2, float slope2, const stc_dropout* drop, void* stream);
+int stc_conv_bn_fwd_drop(int dtype, int kind, int B, stc_view x, int Cin, const void* w_packed, int Cout, stc_view y,
+                         float* fws, int nchunks, const float* gamma, const float* beta, float* running_mean,
+                         float* running_var, int64_t* num_batches_tracked, float momentum, float eps,
+                         stc_view apply_x, stc_view y1, float slope1, stc_view y2, float slope2,
+                         const stc_dropout* drop, void* workspace, int64_t workspace_bytes, void* stream);
+/* stc_bn_bwd_reduce / stc_bn_bwd_apply with g1 (required; the gradient that reaches the BatchNorm output through the
+ * dropout) multiplied by keep/(1-p): dn = g1 * keep/(1-p) * act1'(n) + g2 * act2'(n).  BN tables required.   */
+int stc_bn_bwd_reduce_drop(int dtype, int B, stc_view x, int C,
+                           const float* scale, const float* shift, const float* mean, const float* rstd,
+                           stc_view g1, float slope1, stc_view g2, float slope2, const stc_dropout* drop,
+                           float* part2, int nchunks, void* stream);
+int stc_bn_bwd_apply_drop(int dtype, int B, stc_view x, int C,
+                          const float* scale, const float* shift, const float* mean, const float* rstd,
+                          const float* gamma,
+                          stc_view g1, float slope1, stc_view g2, float slope2, const stc_dropout* drop,
+                          const float* part2, int nchunks,
+                          stc_view dx, float* dgamma, float* dbeta, void* stream);
 
 /* y = tanh(q) stored NCHW fp32 (the generator output).  dq = gy*(1-y^2) into NHWC
  * view dq; dbias[c] = sum dq (deterministic).                               */

@@ -27,6 +27,10 @@ ap.add_argument("--ab", default="", help="comma list of wgrad-overlap settings c
 ap.add_argument("--ab-attr", default="", help="name=v1,v2: trainer attribute (int) cycled per repeat (same process)")
 ap.add_argument("--ab-plans", default="", help="JSON list of {name, conv: [[key..., cfg, ks]], wgrad: [[key..., cfg, "
                 "splits]]} plan-override settings cycled per repeat (same process)")
+ap.add_argument("--use-dropout", type=int, default=0, help="1: generators with use_dropout=True (p = --droprate)")
+ap.add_argument("--droprate", type=float, default=0.5)
+ap.add_argument("--ab-dropout", action="store_true", help="a second trainer with use_dropout=True; the two are "
+                "timed alternately, one per repeat (same process)")
 args = ap.parse_args()
 engine.WGRAD_OVERLAP = args.wgrad_overlap > 0
 if args.wgrad_overlap > 1:
@@ -34,21 +38,31 @@ if args.wgrad_overlap > 1:
 a = types.SimpleNamespace(devices=["cuda:0"], tasks=["train"], lr_G=5e-5, lr_D=2e-5, beta1=0.5, beta2=0.999,
                           D_loss_fn="standard", D_loss_type="normal", ngf=64, dtype=args.dtype, load_weights_g1=None,
                           load_weights_g2=None, load_weights_d1=None, load_weights_d2=None,
-                          streams=bool(args.streams), fused_objectives=bool(args.fused))
+                          streams=bool(args.streams), fused_objectives=bool(args.fused),
+                          use_dropout=bool(args.use_dropout), droprate=args.droprate)
 torch.manual_seed(1234)
 tr = STCGAN(a)
+drop_trs = None
+if args.ab_dropout:
+    a_d = types.SimpleNamespace(**{**vars(a), "use_dropout": True})
+    drop_trs = [tr, STCGAN(a_d)]
 import stcgan_amd.stcgan as _st  # noqa: E402
-tr.set_early = lambda v: setattr(_st, "EARLY_D_BACKWARD", int(v))  # (--ab-attr early=0,1,2)
-tr.set_late = lambda v: setattr(_st, "LATE_STATS_CALLS", bool(v))  # (--ab-attr late=0,1)
-if args.host_sleep_us:
-    _ts = tr.train_step
 
+
+def _slowed(step):
     def _slow(*aa, **kk):
         t_end = time.perf_counter() + args.host_sleep_us * 1e-6
         while time.perf_counter() < t_end:
             pass
-        return _ts(*aa, **kk)
-    tr.train_step = _slow
+        return step(*aa, **kk)
+    return _slow
+
+
+for t_ in drop_trs or [tr]:  # (every trainer: --ab-dropout switches between two)
+    t_.set_early = lambda v: setattr(_st, "EARLY_D_BACKWARD", int(v))  # (--ab-attr early=0,1,2)
+    t_.set_late = lambda v: setattr(_st, "LATE_STATS_CALLS", bool(v))  # (--ab-attr late=0,1)
+    if args.host_sleep_us:
+        t_.train_step = _slowed(t_.train_step)
 dev = torch.device("cuda", 0)
 B = 32
 x = torch.rand((B, 3, 256, 256), device=dev) * 2 - 1
@@ -60,11 +74,18 @@ torch.cuda.synchronize()
 ab = [int(v) for v in args.ab.split(",")] if args.ab else None
 plans = json.loads(args.ab_plans) if args.ab_plans else None
 res = {}
+drop_label = f"use_dropout={args.use_dropout}"
 attr = None
 if args.ab_attr:
     an, av = args.ab_attr.split("=")
     attr = (an, [int(v) for v in av.split(",")])
 for rep in range(args.repeat):
+    if drop_trs:
+        tr = drop_trs[rep % 2]
+        drop_label = f"use_dropout={rep % 2}"
+        for _ in range(2):
+            tr.train_step(x, m, y)
+        torch.cuda.synchronize()
     if attr:
         v = attr[1][rep % len(attr[1])]
         setter = getattr(tr, "set_" + attr[0], None)
@@ -103,8 +124,8 @@ for rep in range(args.repeat):
     torch.cuda.synchronize()
     print(f"{(time.perf_counter() - t0) / args.steps * 1e3:.3f} ms/step  mem {torch.cuda.memory_allocated() / 2**30:.2f} GiB "
           f"reserved {torch.cuda.memory_reserved() / 2**30:.2f} GiB ({args.steps} steps, streams={args.streams}, "
-          f"fused={args.fused}, wgrad_overlap={args.wgrad_overlap})", flush=True)
-    res.setdefault(args.wgrad_overlap, []).append((time.perf_counter() - t0) / args.steps * 1e3)
-if ab or plans or attr:
-    for k, v in res.items():
-        print(f"wgrad_overlap={k}: median {sorted(v)[len(v) // 2]:.3f} ms/step over {len(v)}", flush=True)
+          f"fused={args.fused}, wgrad_overlap={args.wgrad_overlap}, {drop_label})", flush=True)
+    res.setdefault((args.wgrad_overlap, drop_label), []).append((time.perf_counter() - t0) / args.steps * 1e3)
+if ab or plans or attr or drop_trs:
+    for (k, dl), v in res.items():
+        print(f"wgrad_overlap={k}, {dl}: median {sorted(v)[len(v) // 2]:.3f} ms/step over {len(v)}", flush=True)

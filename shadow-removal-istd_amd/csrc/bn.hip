@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "philox.hpp"
 
 namespace stc {
 
@@ -793,6 +794,209 @@ static GradIn mkgrad(stc_view g1, float s1, stc_view g2, float s2) {
 
 static int grid_for(long long work) { return (int)std::max<long long>(1, std::min<long long>((work + 255) / 256, 8192)); }
 
+// ---------------------------------------------------------------- dropout (use_dropout=True generators)
+// The mask function lives in philox.hpp; the kernels below are the general-addressing forms of bn_apply_kernel,
+// bn_bwd_reduce_kernel and bn_bwd_apply_kernel with it applied: same thread layout, same reduction order and the
+// same arithmetic per element, so that with every element kept at scale 1 they write what those kernels write.
+// The mask needs (b, y, x) of every vector, and the three tensors it touches are small (<= 8 MB at bs 32): no
+// streaming form.
+
+// y = act(n * keep/(1-p), slope): the dropout sits between the affine and the activation(s), in fp32
+template <typename T>
+__global__ void __launch_bounds__(256) bn_apply_drop_kernel(View x, PixDiv pd, long long P, int C, const float* scale,
+                                                            const float* shift, View y1, float s1, View y2, float s2,
+                                                            int has2, DropDev drop) {
+  constexpr int N = VW<T>::N;
+  const int CG = C / N;
+  const long long total = P * CG;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const DropKey key = drop_key(drop);
+  struct Off {
+    long long x, y1, y2;
+    unsigned long long li;  // logical index of the vector's first element
+    int c;
+  };
+  auto offs = [&](long long idx) {
+    Off o;
+    const int cg = (int)(idx % CG);
+    const long long pix = idx / CG;
+    o.c = N * cg;
+    int b, yy, xx;
+    pix_bxy(pd, pix, b, yy, xx);
+    o.x = vidx(x, b, yy, xx, o.c);
+    o.y1 = vidx(y1, b, yy, xx, o.c);
+    o.y2 = vidx(y2, b, yy, xx, o.c);
+    o.li = drop_index(drop, C, b, yy, xx, o.c);
+    return o;
+  };
+  auto emit = [&](const Off& o, const float* v0) {
+    float sc[N], sh[N], m[N], v[N], out[N];
+    if (scale) { ldc<N>(scale + o.c, sc); ldc<N>(shift + o.c, sh); }
+    else {
+#pragma unroll
+      for (int e = 0; e < N; ++e) { sc[e] = 1.f; sh[e] = 0.f; }
+    }
+    drop_factor<N>(drop, key, o.li, m);
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      const float n = fmaf(v0[e], sc[e], sh[e]);
+      v[e] = m[e] != 0.f ? n * m[e] : 0.f;
+    }
+#pragma unroll
+    for (int e = 0; e < N; ++e) out[e] = act(v[e], s1);
+    VW<T>::store(reinterpret_cast<T*>(y1.p) + o.y1, out);
+    if (has2) {
+#pragma unroll
+      for (int e = 0; e < N; ++e) out[e] = act(v[e], s2);
+      VW<T>::store(reinterpret_cast<T*>(y2.p) + o.y2, out);
+    }
+  };
+  long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; idx + stride < total; idx += 2 * stride) {  // two 16-byte loads in flight per thread
+    const Off oa = offs(idx), ob = offs(idx + stride);
+    float va[N], vb[N];
+    VW<T>::load(reinterpret_cast<const T*>(x.p) + oa.x, va);
+    VW<T>::load(reinterpret_cast<const T*>(x.p) + ob.x, vb);
+    emit(oa, va);
+    emit(ob, vb);
+  }
+  if (idx < total) {
+    const Off oa = offs(idx);
+    float va[N];
+    VW<T>::load(reinterpret_cast<const T*>(x.p) + oa.x, va);
+    emit(oa, va);
+  }
+}
+
+// bn_bwd_reduce_kernel with g1 * keep/(1-p) (g1 reaches the BN output through the dropout; no mask is stored: it
+// is recomputed from the call's counter): part2[chunk][c] = {sum dn, sum dn*xhat}
+template <typename T>
+__global__ void __launch_bounds__(256) bn_bwd_reduce_drop_kernel(View x, PixDiv pd, long long P, int C,
+                                                                 const float* scale, const float* shift,
+                                                                 const float* mean, const float* rstd, GradIn gi,
+                                                                 float* part, int nchunks, DropDev drop) {
+  constexpr int N = VW<T>::N;
+  const int CG = C / N;
+  const int RL = 256 / CG;
+  const int cg = threadIdx.x % CG, pl = threadIdx.x / CG;
+  const long long per = (P + nchunks - 1) / nchunks;
+  const long long p0 = blockIdx.x * per, p1 = min(P, p0 + per);
+  __shared__ float red[256][2 * N];
+  float a[N], bs[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) { a[e] = 0.f; bs[e] = 0.f; }
+  if (pl < RL) {
+    const int c = N * cg;
+    const DropKey key = drop_key(drop);
+    float sc[N], shf[N], mu[N], rs[N];
+    ldc<N>(scale + c, sc); ldc<N>(shift + c, shf); ldc<N>(mean + c, mu); ldc<N>(rstd + c, rs);
+    // (4 pixels' loads and Philox rounds in flight together; the sums stay in pixel order, as the plain reduce's)
+#pragma unroll 4
+    for (long long pix = p0 + pl; pix < p1; pix += RL) {
+      int b, yy, xx;
+      pix_bxy(pd, pix, b, yy, xx);
+      float v[N], n[N], g[N], m[N], d[N];
+      VW<T>::load(vptr<T>(x, b, yy, xx, c), v);
+      VW<T>::load(vptr<T>(gi.g1, b, yy, xx, c), g);
+      drop_factor<N>(drop, key, drop_index(drop, C, b, yy, xx, c), m);
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        n[e] = fmaf(v[e], sc[e], shf[e]);
+        d[e] = 0.f;
+        d[e] += (g[e] * m[e]) * dact(n[e], gi.s1);
+      }
+      if (gi.has2) {
+        VW<T>::load(vptr<T>(gi.g2, b, yy, xx, c), g);
+#pragma unroll
+        for (int e = 0; e < N; ++e) d[e] += g[e] * dact(n[e], gi.s2);
+      }
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        a[e] += d[e];
+        bs[e] += d[e] * (v[e] - mu[e]) * rs[e];
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < N; ++e) { red[threadIdx.x][e] = a[e]; red[threadIdx.x][N + e] = bs[e]; }
+  __syncthreads();
+  if (pl == 0) {
+    float r0[N], r1[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) { r0[e] = 0.f; r1[e] = 0.f; }
+    for (int k = 0; k < RL; ++k) {
+      const int t = k * CG + cg;
+#pragma unroll
+      for (int e = 0; e < N; ++e) { r0[e] += red[t][e]; r1[e] += red[t][N + e]; }
+    }
+#pragma unroll
+    for (int e = 0; e < N; ++e)
+      *reinterpret_cast<float2*>(part + ((long long)blockIdx.x * C + N * cg + e) * 2) = make_float2(r0[e], r1[e]);
+  }
+}
+
+// bn_bwd_apply_kernel (with the BN tables) and the same masked g1:
+// dx = k1*dn - k0 - k2*v   with k1 = gamma*rstd, k2 = k1*rstd*dgamma/P, k0 = k1*(dbeta/P - mean*rstd*dgamma/P)
+template <typename T>
+__global__ void __launch_bounds__(256) bn_bwd_apply_drop_kernel(View x, PixDiv pd, long long P, int C,
+                                                                const float* scale, const float* shift,
+                                                                const float* mean, const float* rstd,
+                                                                const float* gamma, GradIn gi, const float* dgamma,
+                                                                const float* dbeta, View dx, DropDev drop) {
+  constexpr int N = VW<T>::N;
+  const int CG = C / N;
+  const long long total = P * CG;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const float invP = 1.f / (float)P;
+  const DropKey key = drop_key(drop);
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
+    const int c = N * (int)(idx % CG);
+    int b, yy, xx;
+    pix_bxy(pd, idx / CG, b, yy, xx);
+    float v[N], g1[N], g2[N], m[N], d[N];
+    VW<T>::load(vptr<T>(x, b, yy, xx, c), v);
+    VW<T>::load(vptr<T>(gi.g1, b, yy, xx, c), g1);
+    if (gi.has2) VW<T>::load(vptr<T>(gi.g2, b, yy, xx, c), g2);
+    float sc[N], sh[N], mu[N], rs[N], gm[N], dg[N], db[N];
+    ldc<N>(scale + c, sc); ldc<N>(shift + c, sh);
+    ldc<N>(mean + c, mu); ldc<N>(rstd + c, rs); ldc<N>(gamma + c, gm); ldc<N>(dgamma + c, dg); ldc<N>(dbeta + c, db);
+    drop_factor<N>(drop, key, drop_index(drop, C, b, yy, xx, c), m);
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      const float k1 = gm[e] * rs[e];
+      const float k2 = k1 * rs[e] * dg[e] * invP;
+      const float k0 = k1 * (db[e] * invP - mu[e] * rs[e] * dg[e] * invP);
+      const float n = fmaf(v[e], sc[e], sh[e]);
+      float dn = 0.f;
+      dn += (g1[e] * m[e]) * dact(n, gi.s1);
+      if (gi.has2) dn += g2[e] * dact(n, gi.s2);
+      d[e] = fmaf(k1, dn, -fmaf(k2, v[e], k0));
+    }
+    VW<T>::store(reinterpret_cast<T*>(dx.p) + vidx(dx, b, yy, xx, c), d);
+  }
+}
+
+// keep (1) / drop (0) of every element of the full extent [B][H][W][C], 4 channels (one Philox call) per thread
+__global__ void __launch_bounds__(256) dropout_mask_kernel(DropDev drop, long long quads, unsigned char* out) {
+  const DropKey k = drop_key(drop);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += stride) {
+    unsigned keep[4];
+    drop_keep4(drop, k, (unsigned long long)q * 4, keep);
+    *reinterpret_cast<unsigned*>(out + q * 4) = keep[0] | (keep[1] << 8) | (keep[2] << 16) | (keep[3] << 24);
+  }
+}
+
+// one call's counter: call = {seed, offset}, then offset += 1 (a single lane; ordered by the stream)
+__global__ void dropout_next_kernel(long long* state, long long* call) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const long long seed = state[0], off = state[1];
+    call[0] = seed;
+    call[1] = off;
+    state[1] = off + 1;
+  }
+}
+
 }  // namespace stc
 
 using namespace stc;
@@ -935,6 +1139,141 @@ extern "C" int stc_bn_bwd_apply(int dtype, int B, stc_view x, int C, const float
   if (dtype == STC_F32) { if (dense) STC_BB(float, true); else STC_BB(float, false); }
   else { if (dense) STC_BB(bf16, true); else STC_BB(bf16, false); }
 #undef STC_BB
+  STC_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- dropout (use_dropout=True generators): philox.hpp holds the mask function
+static int mkdrop(const stc_dropout* d, int B, int C, DropDev* out, const char* who) {
+  STC_REQUIRE(d && d->state, "%s: dropout block with a device {seed, offset} required", who);
+  STC_REQUIRE(d->p >= 0.0 && d->p < 1.0, "%s: drop probability %g outside [0, 1)", who, d->p);
+  STC_REQUIRE(d->level >= 0 && d->H > 0 && d->W > 0 && B > 0 && C > 0 && C % 4 == 0,
+              "%s: bad dropout level %d / extent %d x %d x %d x %d (C %% 4 == 0)", who, d->level, B, d->H, d->W, C);
+  STC_REQUIRE((long long)B * d->H * d->W * C < (1ll << 34), "%s: more than 2^34 elements under one dropout level", who);
+  out->state = reinterpret_cast<const unsigned long long*>(d->state);
+  out->level = (unsigned)d->level;
+  out->thresh = (unsigned)(unsigned long long)(d->p * 4294967296.0);  // floor(p * 2^32)
+  out->scale = (float)(1.0 / (1.0 - d->p));
+  out->H = d->H; out->W = d->W;
+  return 0;
+}
+
+extern "C" int stc_dropout_next(int64_t* state, int64_t* call_state, void* stream) {
+  STC_REQUIRE(state && call_state, "stc_dropout_next: state and call_state required");
+  hipLaunchKernelGGL(dropout_next_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (long long*)state,
+                     (long long*)call_state);
+  STC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stc_dropout_mask(const stc_dropout* drop, int B, int C, uint8_t* out, void* stream) {
+  DropDev dd;
+  if (int rc = mkdrop(drop, B, C, &dd, "stc_dropout_mask")) return rc;
+  STC_REQUIRE(out, "stc_dropout_mask: output required");
+  const long long quads = (long long)B * drop->H * drop->W * C / 4;
+  hipLaunchKernelGGL(dropout_mask_kernel, dim3(grid_for(quads)), dim3(256), 0, (hipStream_t)stream, dd, quads, out);
+  STC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stc_bn_apply_drop(int dtype, int B, stc_view x, int C, const float* scale, const float* shift,
+                                 stc_view y1, float slope1, stc_view y2, float slope2, const stc_dropout* drop,
+                                 void* stream) {
+  STC_REQUIRE((scale == nullptr) == (shift == nullptr), "stc_bn_apply_drop: scale/shift must come together");
+  STC_REQUIRE(y1.p && vec_ok(dtype, C, x) && vec_ok(dtype, C, y1) && (!y2.p || vec_ok(dtype, C, y2)),
+              "stc_bn_apply_drop: C=%d / views not 16-byte vectorisable NHWC", C);
+  DropDev dd;
+  if (int rc = mkdrop(drop, B, C, &dd, "stc_bn_apply_drop")) return rc;
+  STC_REQUIRE(x.H <= drop->H && x.W <= drop->W, "stc_bn_apply_drop: view %d x %d outside the dropout extent %d x %d",
+              x.H, x.W, drop->H, drop->W);
+  hipStream_t st = (hipStream_t)stream;
+  View v = mkview(x), o1 = mkview(y1), o2 = y2.p ? mkview(y2) : mkview(y1);
+  const PixDiv pd = mkpix(B, x.H, x.W);
+  const long long P = (long long)B * x.H * x.W;
+  const int N = dtype == STC_F32 ? 4 : 8;
+  const int blocks = grid_for(P * (C / N));  // covers the tensor once at the generator's sizes (launch-latency bound)
+  const int h2 = y2.p != nullptr ? 1 : 0;
+  if (dtype == STC_F32)
+    hipLaunchKernelGGL(bn_apply_drop_kernel<float>, dim3(blocks), dim3(256), 0, st, v, pd, P, C, scale, shift, o1, slope1, o2, slope2, h2, dd);
+  else
+    hipLaunchKernelGGL(bn_apply_drop_kernel<bf16>, dim3(blocks), dim3(256), 0, st, v, pd, P, C, scale, shift, o1, slope1, o2, slope2, h2, dd);
+  STC_CHECK_LAUNCH();
+  return 0;
+}
+
+// stc_conv_bn_fwd with the dropout-aware apply: the same three launches from one call
+extern "C" int stc_conv_bn_fwd_drop(int dtype, int kind, int B, stc_view x, int Cin, const void* w_packed, int Cout,
+                                    stc_view y, float* fws, int nchunks, const float* gamma, const float* beta,
+                                    float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                    float momentum, float eps, stc_view apply_x, stc_view y1, float slope1,
+                                    stc_view y2, float slope2, const stc_dropout* drop, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+  STC_REQUIRE(fws && nchunks > 0 && gamma && beta, "stc_conv_bn_fwd_drop: statistics workspace and BN affine required");
+  STC_REQUIRE(y1.p, "stc_conv_bn_fwd_drop: an apply output is required");
+  DropDev dd;
+  if (int rc = mkdrop(drop, B, Cout, &dd, "stc_conv_bn_fwd_drop")) return rc;  // (before anything is launched)
+  int rc = stc_conv_fwd_ex(dtype, kind, B, x, Cin, w_packed, Cout, y, nullptr, 0, 0, fws, nchunks, nullptr, workspace,
+                           workspace_bytes, stream);
+  if (rc) return rc;
+  float* tab = fws + (int64_t)nchunks * Cout * 4;
+  rc = stc_bn_finalize(fws, nchunks, Cout, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps,
+                       tab, tab + Cout, tab + 2 * Cout, tab + 3 * Cout, stream);
+  if (rc) return rc;
+  return stc_bn_apply_drop(dtype, B, apply_x, Cout, tab + 2 * Cout, tab + 3 * Cout, y1, slope1, y2, slope2, drop,
+                           stream);
+}
+
+extern "C" int stc_bn_bwd_reduce_drop(int dtype, int B, stc_view x, int C, const float* scale, const float* shift,
+                                      const float* mean, const float* rstd, stc_view g1, float slope1, stc_view g2,
+                                      float slope2, const stc_dropout* drop, float* part2, int nchunks, void* stream) {
+  STC_REQUIRE(vec_ok(dtype, C, x) && g1.p && vec_ok(dtype, C, g1) && (!g2.p || vec_ok(dtype, C, g2)),
+              "stc_bn_bwd_reduce_drop: bad C=%d / views (g1 required)", C);
+  STC_REQUIRE(scale && shift && mean && rstd, "stc_bn_bwd_reduce_drop: BN tables required");
+  DropDev dd;
+  if (int rc = mkdrop(drop, B, C, &dd, "stc_bn_bwd_reduce_drop")) return rc;
+  STC_REQUIRE(x.H <= drop->H && x.W <= drop->W, "stc_bn_bwd_reduce_drop: view outside the dropout extent");
+  hipStream_t st = (hipStream_t)stream;
+  GradIn gi = mkgrad(g1, slope1, g2, slope2);
+  View v = mkview(x);
+  const PixDiv pd = mkpix(B, x.H, x.W);
+  const long long P = (long long)B * x.H * x.W;
+  if (dtype == STC_F32)
+    hipLaunchKernelGGL(bn_bwd_reduce_drop_kernel<float>, dim3(nchunks), dim3(256), 0, st, v, pd, P, C, scale, shift, mean, rstd, gi, part2, nchunks, dd);
+  else
+    hipLaunchKernelGGL(bn_bwd_reduce_drop_kernel<bf16>, dim3(nchunks), dim3(256), 0, st, v, pd, P, C, scale, shift, mean, rstd, gi, part2, nchunks, dd);
+  STC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stc_bn_bwd_apply_drop(int dtype, int B, stc_view x, int C, const float* scale, const float* shift,
+                                     const float* mean, const float* rstd, const float* gamma, stc_view g1,
+                                     float slope1, stc_view g2, float slope2, const stc_dropout* drop,
+                                     const float* part2, int nchunks, stc_view dx, float* dgamma, float* dbeta,
+                                     void* stream) {
+  STC_REQUIRE(vec_ok(dtype, C, x) && vec_ok(dtype, C, dx) && g1.p && vec_ok(dtype, C, g1) &&
+                  (!g2.p || vec_ok(dtype, C, g2)),
+              "stc_bn_bwd_apply_drop: bad C=%d / views (g1 required)", C);
+  STC_REQUIRE(mean && part2 && nchunks > 0 && dgamma && dbeta && gamma && rstd && scale && shift,
+              "stc_bn_bwd_apply_drop: missing BN tensors");
+  DropDev dd;
+  if (int rc = mkdrop(drop, B, C, &dd, "stc_bn_bwd_apply_drop")) return rc;
+  STC_REQUIRE(x.H <= drop->H && x.W <= drop->W, "stc_bn_bwd_apply_drop: view outside the dropout extent");
+  hipStream_t st = (hipStream_t)stream;
+  GradIn gi = mkgrad(g1, slope1, g2, slope2);
+  if (nchunks <= 256)
+    hipLaunchKernelGGL(bn_bwd_finalize_wave_kernel, dim3((C + 3) / 4), dim3(256), 0, st, part2, nchunks, C, dgamma, dbeta);
+  else
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, part2, nchunks, C, dgamma, dbeta);
+  STC_CHECK_LAUNCH();
+  View v = mkview(x), o = mkview(dx);
+  const PixDiv pd = mkpix(B, x.H, x.W);
+  const long long P = (long long)B * x.H * x.W;
+  const int N = dtype == STC_F32 ? 4 : 8;
+  const int blocks = grid_for(P * (C / N));
+  if (dtype == STC_F32)
+    hipLaunchKernelGGL(bn_bwd_apply_drop_kernel<float>, dim3(blocks), dim3(256), 0, st, v, pd, P, C, scale, shift, mean, rstd, gamma, gi, dgamma, dbeta, o, dd);
+  else
+    hipLaunchKernelGGL(bn_bwd_apply_drop_kernel<bf16>, dim3(blocks), dim3(256), 0, st, v, pd, P, C, scale, shift, mean, rstd, gamma, gi, dgamma, dbeta, o, dd);
   STC_CHECK_LAUNCH();
   return 0;
 }

@@ -43,6 +43,13 @@ class PackDesc(ctypes.Structure):
     _fields_ = [("mode", ctypes.c_int32), ("P", ctypes.c_int32), ("Q", ctypes.c_int32), ("N_pad", ctypes.c_int32),
                 ("C_pad", ctypes.c_int32), ("pad_", ctypes.c_int32), ("W", ctypes.c_void_p), ("out", ctypes.c_void_p)]
 
+
+class Dropout(ctypes.Structure):
+    """stc_dropout: one dropout level of one generator call (state: that call's device {seed, offset})."""
+    _fields_ = [("state", ctypes.c_void_p), ("p", ctypes.c_double), ("level", ctypes.c_int32),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 
 # name: (restype, argtypes)
@@ -83,6 +90,15 @@ _SIGS = {
                                  _vp]),
     "stc_bn_bwd_apply": (_i32, [_i32, _i32, View, _i32, _vp, _vp, _vp, _vp, _vp, View, _f32, View, _f32, _vp, _i32,
                                 View, _vp, _vp, _vp]),
+    "stc_dropout_next": (_i32, [_vp, _vp, _vp]),
+    "stc_dropout_mask": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "stc_bn_apply_drop": (_i32, [_i32, _i32, View, _i32, _vp, _vp, View, _f32, View, _f32, _vp, _vp]),
+    "stc_conv_bn_fwd_drop": (_i32, [_i32, _i32, _i32, View, _i32, _vp, _i32, View, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                    _f32, _f32, View, View, _f32, View, _f32, _vp, _vp, _i64, _vp]),
+    "stc_bn_bwd_reduce_drop": (_i32, [_i32, _i32, View, _i32, _vp, _vp, _vp, _vp, View, _f32, View, _f32, _vp, _vp,
+                                      _i32, _vp]),
+    "stc_bn_bwd_apply_drop": (_i32, [_i32, _i32, View, _i32, _vp, _vp, _vp, _vp, _vp, View, _f32, View, _f32, _vp, _vp,
+                                     _i32, View, _vp, _vp, _vp]),
     "stc_tanh_bias_bwd": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, View, _vp, _vp, _i32, _vp]),
     "stc_gather_nchw": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, View, _i32, _vp]),
     "stc_scatter_nchw": (_i32, [_i32, _i32, _i32, _i32, View, _i32, _vp, _vp, _vp]),

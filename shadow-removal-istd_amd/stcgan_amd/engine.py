@@ -19,6 +19,8 @@ channels, S[k] the block-k input resolution (S[1] = S[0]//2, S[k+1] = ceil(S[k]/
   rq[k]  raw convT_k output q_k                   (res 2*S[k+1] = padded S[k])
   cr[k]  [ ReLU(BN_d(r_k)) | ReLU(BN_u(q_{k+1})) ] -> input of convT_k
          (networks.py:108,143: ReLU of the concat; ReLU(LeakyReLU(v)) = ReLU(v))
+         use_dropout, train mode, the levels right above the innermost one: ReLU(BN_u(q_{k+1}) * keep/(1-p)), the
+         mask a counter-based function of logical indices (GenPlan.drop, ops.dropout_next)
   y = tanh(convT_0(cr[0]) + bias), written NCHW fp32.
 """
 import torch
@@ -213,7 +215,7 @@ class GenPlan:
         outer = net.model  # outermost UnetSkipConnectionBlock
         self.in_c = outer.model[0].in_channels
         self.out_c = outer.model[3].out_channels
-        conv, bnd, convT, bnu = [], {}, {}, {}
+        conv, bnd, convT, bnu, drop = [], {}, {}, {}, {}
         conv.append(outer.model[0])
         convT[0] = outer.model[3]
         blk = outer.model[1]
@@ -228,10 +230,18 @@ class GenPlan:
             bnd[k] = seq[2]
             convT[k] = seq[5]
             bnu[k] = seq[6]
+            if isinstance(seq[-1], torch.nn.Dropout):  # use_dropout: after the up-norm (networks.py)
+                p = seq[-1].p
+                if not 0.0 <= p < 1.0:
+                    raise ValueError(f"stcgan_amd: dropout probability must satisfy 0 <= p < 1, got {p!r}")
+                if p > 0.0:  # (p = 0 keeps everything and, as torch's dropout, draws nothing: the plain path)
+                    drop[k] = float(p)
             blk = seq[3]
             k += 1
         self.L = len(conv)
         self.conv, self.bnd, self.convT, self.bnu = conv, bnd, convT, bnu
+        # {level k: p}: train-mode dropout on the output of BN_up[k] (the blocks right above the innermost one)
+        self.drop = drop
         self.co = [c.out_channels for c in conv]
         self.params = list(net.parameters())
 
@@ -263,12 +273,15 @@ def _conv_bn(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev):
     return t, st
 
 
-def _conv_bn_act(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev, apply_x, y1, s1, y2=None, s2=0.0, defer=None):
+def _conv_bn_act(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev, apply_x, y1, s1, y2=None, s2=0.0, defer=None,
+                 drop=None):
     """Conv -> BatchNorm2d -> activation pass of ``apply_x`` into y1 [and y2] (y1 None: none); returns _conv_bn's
     (table, (mean, rstd) or None).  Train mode: one library call (ops.conv_bn_act); ``defer`` (a list): the running
-    statistics are not updated, the update's inputs are appended (ops.bn_running_update)."""
+    statistics are not updated, the update's inputs are appended (ops.bn_running_update); ``drop`` (train mode
+    only): a dropout level between the BatchNorm and the activation (ops.dropout_next)."""
     if train:
-        return ops.conv_bn_act(kind, B, xv, cin, w, cout, yv, dt, bn, apply_x, y1, s1, y2, s2, defer=defer)
+        return ops.conv_bn_act(kind, B, xv, cin, w, cout, yv, dt, bn, apply_x, y1, s1, y2, s2, defer=defer, drop=drop)
+    assert drop is None, "dropout is the identity in eval mode"
     t, st = _conv_bn(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev)
     if y1 is not None:
         ops.bn_apply(B, apply_x, cout, dt, (t[0], t[1]), y1, s1, y2, s2)
@@ -299,9 +312,19 @@ def gen_forward(plan, sources, train, dt, cache, save):
     rq = [None] + [_nhwc(B, *_pad2(S, k), co[k - 1], dt, dev) for k in range(1, Lv)]
     tab_d, tab_u, st_d, st_u = {}, {}, {}, {}
 
-    def conv_bn_act(kind, xv, cin_, w, cout, yv, bn, apply_x, y1, s1, y2=None, s2=0.0):
+    def conv_bn_act(kind, xv, cin_, w, cout, yv, bn, apply_x, y1, s1, y2=None, s2=0.0, drop=None):
         """conv -> BatchNorm (batch statistics fused into the conv in train mode) -> activation pass."""
-        return _conv_bn_act(kind, B, xv, cin_, w, cout, yv, dt, bn, train, dev, apply_x, y1, s1, y2, s2)
+        return _conv_bn_act(kind, B, xv, cin_, w, cout, yv, dt, bn, train, dev, apply_x, y1, s1, y2, s2, drop=drop)
+
+    # use_dropout, train mode: this call's {seed, offset} copy (one tiny launch; the generator's offset advances),
+    # read from device memory by every dropout kernel of the call, forward and backward
+    drop_state = ops.dropout_next(plan.net._dropout_tensor(dev)) if (train and plan.drop) else None
+
+    def drop_of(k):
+        """The dropout level on BN_up[k]'s output, over the full ConvT extent (before the crop), or None."""
+        if drop_state is None or k not in plan.drop:
+            return None
+        return (drop_state, k, plan.drop[k]) + _pad2(S, k)
 
     # ---- down path
     w0 = ops.packed(cache, plan.conv[0].weight, L.PACK_CONV_FWD, co[0], cin_pad, dt)
@@ -329,7 +352,7 @@ def gen_forward(plan, sources, train, dt, cache, save):
         # statistics over the full ConvT extent (before the crop of an odd level)
         tab_u[k], st_u[k] = conv_bn_act(L.CONVT_S2, L.nhwc_view(cr[k]), cin_t(k), wt, co[k - 1], L.nhwc_view(rq[k]),
                                         plan.bnu[k], L.nhwc_view(rq[k], 0, *S[k]), L.nhwc_view(cr[k - 1], co[k - 1]),
-                                        0.0)
+                                        0.0, drop=drop_of(k))
     # ---- outermost: tanh(convT_0(cr[0]) + bias) -> NCHW fp32
     Ho, Wo = 2 * S[1][0], 2 * S[1][1]
     y = torch.empty((B, plan.out_c, Ho, Wo), dtype=torch.float32, device=dev)
@@ -340,6 +363,8 @@ def gen_forward(plan, sources, train, dt, cache, save):
     if save:
         saved = dict(S=S, xin=xin, rd=rd, ad=ad, cr=cr, rq=rq, tab_d=tab_d, tab_u=tab_u, st_d=st_d, st_u=st_u,
                      y=y, cin=cin, cin_pad=cin_pad, src_c=[s.shape[1] for s in sources])
+        if drop_state is not None:
+            saved["drop"] = {k: drop_of(k) for k in plan.drop}
         if TRACE is not None:
             _trace_new("G")
             _trace("G", "saved", saved)
@@ -357,6 +382,7 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
     gy = gy.contiguous()
     need_w = W is not None
     lane = _WgradLane() if need_w else None
+    drops = saved.get("drop") or {}  # {level: dropout level of the forward call} (use_dropout, train mode)
 
     def dest(p):
         return W.dest(p) if need_w else None
@@ -402,6 +428,21 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
         t = tab_u[k + 1]
         dq = _nhwc(B, ah, aw, C, dt, dev)
         bn = plan.bnu[k + 1]
+        drop = drops.get(k + 1)
+        if drop is not None:
+            # a dropout level: the gradient reaches BN_up[k+1]'s output through the mask, g * [n > 0] * keep/(1-p).
+            # The unfused form -- the conv writes gcat[k], then the dropout-aware BN backward recomputes the mask
+            # from the call's counter (the GEMM epilogues know nothing of it; two small element-wise launches more)
+            ops.conv(L.CONV_S2, B, dqv, cg, wd, cin_t, L.nhwc_view(gcat[k], 0, *S[k + 1]), dt)
+            if need_w:
+                W.done([plan.convT[k].weight], lane)
+            ops.bn_backward(B, L.nhwc_view(rq[k + 1]), C, dt, L.nhwc_view(dq), g1=L.nhwc_view(gcat[k], C), s1=0.0,
+                            bn_state=(t[0], t[1], mean, rstd, bn.weight), dgamma=dest(bn.weight),
+                            dbeta=dest(bn.bias), drop=drop)
+            if need_w:
+                W.done([bn.weight, bn.bias])
+            _trace("G", ("dq", k + 1), dq)
+            continue
         ops.conv_bn_backward(L.CONV_S2, B, dqv, cg, wd, cin_t, L.nhwc_view(gcat[k], 0, *S[k + 1]), dt,
                              bn_x=L.nhwc_view(rq[k + 1]), C=C, bn_state=(t[0], t[1], mean, rstd),
                              gamma=bn.weight, s_self=0.0, ch_off=C, dxv=L.nhwc_view(dq),

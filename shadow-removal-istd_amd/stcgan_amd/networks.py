@@ -8,7 +8,8 @@ network runs the whole network as hand-written HIP kernels
 (``engine.gen_forward`` / ``engine.disc_forward``) behind one autograd node.
 
 Differences from the reference that a caller can observe: none in values
-(parity-tested); odd spatial sizes follow the pad/crop generator of
+(parity-tested; ``use_dropout=True`` draws its train-mode masks from a counter-based
+generator of its own, ``set_dropout_seed`` / ``dropout_state``, not torch's); odd spatial sizes follow the pad/crop generator of
 src/models/stcgan_g.py:120-132 (the STCGAN/networks.py version raises there);
 forward also accepts a list/tuple of NCHW tensors, treated as their channel
 concatenation without materialising it (what ``torch.cat(..., 1)`` would give).
@@ -42,6 +43,13 @@ def get_generator(*args, **kwargs):
 
 def get_discriminator(*args, **kwargs):
     return NLayerDiscriminator(*args, **kwargs)
+
+
+def check_drop_rate(p):
+    """A dropout probability as a float, 0 <= p < 1 (ValueError otherwise)."""
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"stcgan_amd: dropout probability must be a number with 0 <= p < 1, got {p!r}")
+    return float(p)
 
 
 class _HipNet(nn.Module):
@@ -113,17 +121,22 @@ class UnetGenerator(_HipNet):
     kind = "G"
 
     def __init__(self, in_channels, out_channels, ngf=64, num_downs=8, norm_layer=nn.BatchNorm2d,
-                 use_dropout=False):
+                 use_dropout=False, drop_rate=None):
+        """use_dropout: nn.Dropout after the up-norm of the num_downs - 5 blocks above the innermost one, as the
+        reference (p = 0.5; ``drop_rate`` overrides it, 0 <= drop_rate < 1).  Train mode only; the masks are a
+        counter-based function of this generator's {seed, offset} (set_dropout_seed / dropout_state).  p is read
+        from the nn.Dropout modules when the launch plan is made (the first forward, and again after a module move):
+        set_drop_rate changes it later; writing ``Dropout.p`` by hand does not reach an existing plan."""
         super().__init__()
         if norm_layer is not nn.BatchNorm2d:
             raise NotImplementedError("stcgan_amd: only nn.BatchNorm2d is on the ST-CGAN path")
-        if use_dropout:
-            raise NotImplementedError("stcgan_amd: use_dropout is not on the ST-CGAN path (STCGAN/stcgan.py:34-37)")
+        p = check_drop_rate(0.5 if drop_rate is None else drop_rate)
+        self._drop_state = None  # device int64 {seed, offset}: a plain attribute, the state_dict keys stay the reference's
         unet_block = UnetSkipConnectionBlock(ngf * 8, ngf * 8, input_nc=None, submodule=None,
                                              norm_layer=norm_layer, innermost=True)
         for _ in range(num_downs - 5):
             unet_block = UnetSkipConnectionBlock(ngf * 8, ngf * 8, input_nc=None, submodule=unet_block,
-                                                 norm_layer=norm_layer, use_dropout=use_dropout)
+                                                 norm_layer=norm_layer, use_dropout=bool(use_dropout), drop_rate=p)
         unet_block = UnetSkipConnectionBlock(ngf * 4, ngf * 8, input_nc=None, submodule=unet_block,
                                              norm_layer=norm_layer)
         unet_block = UnetSkipConnectionBlock(ngf * 2, ngf * 4, input_nc=None, submodule=unet_block,
@@ -136,6 +149,52 @@ class UnetGenerator(_HipNet):
     def _make_plan(self):
         return engine.GenPlan(self)
 
+    def _apply(self, fn, *args, **kwargs):
+        if self._drop_state is not None:  # the counter moves with the module (a plain attribute: not in _buffers)
+            self._drop_state = fn(self._drop_state)
+        return super()._apply(fn, *args, **kwargs)
+
+    def _dropout_tensor(self, device):
+        """The device int64 {seed, offset}; made at first use with the seed torch.initial_seed() + rank."""
+        st = self._drop_state
+        if st is None or st.device != device:
+            from . import parallel
+            seed, off = ((int(v) for v in st.tolist()) if st is not None else
+                         (ops.dropout_rank_seed(torch.initial_seed(), parallel.rank()), 0))
+            st = self._drop_state = ops.dropout_state_tensor(seed, off, device)
+        return st
+
+    def set_dropout_seed(self, seed, offset=0):
+        """Set the dropout {seed, offset} (64-bit seed; offset = the number of train-mode forwards drawn so far).
+        Written in place once the state exists, so a captured graph keeps reading it."""
+        dev = next(self.parameters()).device
+        new = ops.dropout_state_tensor(seed, offset, dev)
+        if self._drop_state is not None and self._drop_state.device == dev:
+            self._drop_state.copy_(new)
+        else:
+            self._drop_state = new
+        return self
+
+    def set_drop_rate(self, p):
+        """Set the drop probability (0 <= p < 1) of every nn.Dropout of this generator; the launch plan, which
+        caches it, is made again at the next forward."""
+        p = check_drop_rate(p)
+        for m in self.modules():
+            if isinstance(m, nn.Dropout):
+                m.p = p
+        self._plan = None
+        return self
+
+    def dropout_state(self):
+        """(seed, offset) as Python ints (a host sync); the seed unsigned.  Not a pure read on a generator whose state
+        does not exist yet: like the first train-mode forward it creates it, fixing the default seed
+        torch.initial_seed() + rank as of this call.  That default is the same for every generator of a process, so
+        two stand-alone generators that are never given seeds draw the same masks at equal level and shape: give
+        them distinct seeds (set_dropout_seed), as the trainer does."""
+        dev = next(self.parameters()).device
+        seed, off = (int(v) for v in self._dropout_tensor(dev).tolist())
+        return seed & 0xFFFFFFFFFFFFFFFF, off
+
     def forward(self, input):
         """Standard forward: input NCHW fp32 (or a list of NCHW tensors to concatenate)."""
         return self._run(input)
@@ -146,7 +205,7 @@ class UnetSkipConnectionBlock(nn.Module):
     Executed only as part of UnetGenerator (the whole U-Net is one fused HIP schedule)."""
 
     def __init__(self, outer_nc, inner_nc, input_nc=None, submodule=None, outermost=False, innermost=False,
-                 norm_layer=nn.BatchNorm2d, use_dropout=False):
+                 norm_layer=nn.BatchNorm2d, use_dropout=False, drop_rate=0.5):
         super().__init__()
         self.outermost = outermost
         self.innermost = innermost
@@ -167,6 +226,8 @@ class UnetSkipConnectionBlock(nn.Module):
         else:
             upconv = nn.ConvTranspose2d(inner_nc * 2, outer_nc, kernel_size=4, stride=2, padding=1, bias=use_bias)
             model = [downrelu, downconv, downnorm, submodule, uprelu, upconv, upnorm]
+            if use_dropout:  # last, as the reference: indices 0-6 and every state_dict key unchanged
+                model.append(nn.Dropout(check_drop_rate(drop_rate)))
         self.model = nn.Sequential(*model)
 
     def forward(self, x):

@@ -239,12 +239,14 @@ def conv_stats(kind, B, xv, cin, w_packed, cout, yv, dt, bias=None, force=None):
     return part, nch
 
 
-def conv_bn_act(kind, B, xv, cin, w_packed, cout, yv, dt, bn, apply_x, y1, s1, y2=None, s2=0.0, defer=None):
+def conv_bn_act(kind, B, xv, cin, w_packed, cout, yv, dt, bn, apply_x, y1, s1, y2=None, s2=0.0, defer=None,
+                drop=None):
     """A BatchNorm layer's train-mode forward: conv into ``yv`` with the batch statistics, the BN finalize (running
     statistics updated) and the activation pass of ``apply_x`` into y1 [and y2] (y1 None: no pass) -- one library call
     (stc_conv_bn_fwd; the instrumented / forced-plan runs take the three separate calls).  Returns ((2, cout) scale /
     shift table, (mean, rstd)), views of one fp32 buffer.  defer (a list): the running statistics are left alone and
-    (partials, chunks, cout, bn) is appended for bn_running_update."""
+    (partials, chunks, cout, bn) is appended for bn_running_update.  drop (a dropout level, see dropout_next): the
+    activation pass applies the dropout mask (stc_conv_bn_fwd_drop, the same launches)."""
     dev = w_packed.device
     gh, gw = (xv.H, xv.W) if kind == L.CONVT_S2 else (yv.H, yv.W)
     upd = defer is None
@@ -255,13 +257,25 @@ def conv_bn_act(kind, B, xv, cin, w_packed, cout, yv, dt, bn, apply_x, y1, s1, y
         if not upd:
             defer.append((part, nch, cout, bn))
         if y1 is not None:
-            bn_apply(B, apply_x, cout, dt, (t[0], t[1]), y1, s1, y2, s2)
+            bn_apply(B, apply_x, cout, dt, (t[0], t[1]), y1, s1, y2, s2, drop=drop)
         return t, st
     nbytes, nch, _ = conv_query(kind, B, gh, gw, cin, cout, dt)
     ws, nb = _ws(nbytes, dev)
     P = nch * cout * 4
     fws = torch.empty(P + 4 * cout, dtype=torch.float32, device=dev)
     mom = bn.momentum if bn.momentum is not None else BN_MOMENTUM
+    if drop is not None:
+        d = _drop(drop)
+        check(lib().stc_conv_bn_fwd_drop(L.dtype_code(dt), kind, B, xv, cin, ptr(w_packed), cout, yv, ptr(fws), nch,
+                                         ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean) if upd else None,
+                                         ptr(bn.running_var) if upd else None,
+                                         ptr(bn.num_batches_tracked) if upd else None, float(mom), float(bn.eps),
+                                         apply_x, y1, float(s1), y2 if y2 is not None else L.NULL_VIEW, float(s2),
+                                         ctypes.byref(d), ptr(ws), nb, stream()), "stc_conv_bn_fwd_drop")
+        if not upd:
+            defer.append((fws, nch, cout, bn))
+        tab = fws[P:]
+        return tab[2 * cout:].view(2, cout), (tab[:cout], tab[cout:2 * cout])
     check(lib().stc_conv_bn_fwd(L.dtype_code(dt), kind, B, xv, cin, ptr(w_packed), cout, yv, ptr(fws), nch,
                                 ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean) if upd else None,
                                 ptr(bn.running_var) if upd else None, ptr(bn.num_batches_tracked) if upd else None,
@@ -273,6 +287,52 @@ def conv_bn_act(kind, B, xv, cin, w_packed, cout, yv, dt, bn, apply_x, y1, s1, y
         defer.append((fws, nch, cout, bn))
     tab = fws[P:]
     return tab[2 * cout:].view(2, cout), (tab[:cout], tab[cout:2 * cout])
+
+
+# ----------------------------------------------------------------------------- dropout (use_dropout=True generators)
+# A dropout level of one generator call is the tuple ``(call_state, level, p, H, W)``: the call's device int64
+# {seed, offset} (dropout_next), the U-Net block, the drop probability and the full ConvT extent the mask's logical
+# index runs over (include/stcgan_hip.h, stc_dropout; csrc/philox.hpp holds the mask function).
+
+
+def dropout_rank_seed(base, rank=0, world=1, net=0):
+    """The 64-bit dropout seed of generator number ``net`` on data-parallel rank ``rank``: distinct for every
+    (net, rank) of one run -- base + net * world + rank, modulo 2^64."""
+    return (int(base) + int(net) * int(world) + int(rank)) & 0xFFFFFFFFFFFFFFFF
+
+
+def dropout_state_tensor(seed, offset, device):
+    """The device int64 {seed, offset} of a generator (the unsigned 64-bit seed stored in two's complement)."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return torch.tensor([seed - (1 << 64) if seed >= (1 << 63) else seed, int(offset)], dtype=torch.int64,
+                        device=device)
+
+
+def dropout_next(state):
+    """One call's counter (stc_dropout_next, one tiny launch): returns a new device {seed, offset} copy for every
+    dropout kernel of this call, forward and backward, and advances ``state``'s offset by one."""
+    assert state.dtype == torch.int64 and state.numel() == 2 and state.is_contiguous()
+    call = torch.empty(2, dtype=torch.int64, device=state.device)
+    check(lib().stc_dropout_next(ptr(state), ptr(call), stream()), "stc_dropout_next")
+    return call
+
+
+def _drop(drop):
+    state, level, p, H, W = drop
+    d = L.Dropout(state.data_ptr(), float(p), int(level), int(H), int(W), 0)
+    d._keep = state
+    return d
+
+
+def dropout_mask(state, level, shape, p=0.5):
+    """keep (1) / drop (0) of every element of the NHWC full extent ``shape`` = (B, H, W, C) at ``level`` for the
+    {seed, offset} in ``state`` (device int64[2]) -- the device function the dropout kernels use (stc_dropout_mask).
+    Returns a uint8 NHWC tensor."""
+    B, H, W, C = shape
+    out = torch.empty((B, H, W, C), dtype=torch.uint8, device=state.device)
+    d = _drop((state, level, p, H, W))
+    check(lib().stc_dropout_mask(ctypes.byref(d), B, C, ptr(out), stream()), "stc_dropout_mask")
+    return out
 
 
 def bn_running_update(part, nch, C, bn):
@@ -668,21 +728,33 @@ def bn_eval_table(C, bn, scale_out, shift_out):
                                 ptr(shift_out), stream()), "stc_bn_finalize(eval)")
 
 
-def bn_apply(B, xv, C, dt, table, y1, s1, y2=None, s2=1.0):
-    """y1 = act(x*scale+shift, s1) [, y2 = act(.., s2)]; table = (scale, shift) or None (identity)."""
+def bn_apply(B, xv, C, dt, table, y1, s1, y2=None, s2=1.0, drop=None):
+    """y1 = act(x*scale+shift, s1) [, y2 = act(.., s2)]; table = (scale, shift) or None (identity).
+    drop (a dropout level, see dropout_next): y = act((x*scale+shift) * keep/(1-p), s) (stc_bn_apply_drop)."""
     sc, sh = _pro(table)
+    if drop is not None:
+        d = _drop(drop)
+        check(lib().stc_bn_apply_drop(L.dtype_code(dt), B, xv, C, sc, sh, y1, float(s1),
+                                      y2 if y2 is not None else L.NULL_VIEW, float(s2), ctypes.byref(d), stream()),
+              "stc_bn_apply_drop")
+        return
     check(lib().stc_bn_apply(L.dtype_code(dt), B, xv, C, sc, sh, y1, float(s1),
                              y2 if y2 is not None else L.NULL_VIEW, float(s2), stream()), "stc_bn_apply")
 
 
-def bn_backward(B, xv, C, dt, dxv, g1=None, s1=0.0, g2=None, s2=0.0, bn_state=None, dgamma=None, dbeta=None):
+def bn_backward(B, xv, C, dt, dxv, g1=None, s1=0.0, g2=None, s2=0.0, bn_state=None, dgamma=None, dbeta=None,
+                drop=None):
     """Fused activation + BatchNorm backward.  bn_state = (scale, shift, mean, rstd, gamma) or None
-    (no BN: dx = g1*act1'(x) + g2*act2'(x)).  Returns (dgamma, dbeta) or (None, None)."""
+    (no BN: dx = g1*act1'(x) + g2*act2'(x)).  Returns (dgamma, dbeta) or (None, None).
+    drop (a dropout level, see dropout_next; needs bn_state and g1): g1 reaches the BN output through the dropout,
+    g1 * keep/(1-p) with the mask recomputed from the call's counter (stc_bn_bwd_reduce_drop / _apply_drop)."""
     l = lib()
     g1v = g1 if g1 is not None else L.NULL_VIEW
     g2v = g2 if g2 is not None else L.NULL_VIEW
     dev_t = None
     if bn_state is None:
+        if drop is not None:
+            raise ValueError("bn_backward: the dropout form needs the BatchNorm state")
         check(l.stc_bn_bwd_apply(L.dtype_code(dt), B, xv, C, None, None, None, None, None, g1v, float(s1), g2v,
                                  float(s2), None, 0, dxv, None, None, stream()), "stc_bn_bwd_apply")
         return None, None
@@ -690,6 +762,17 @@ def bn_backward(B, xv, C, dt, dxv, g1=None, s1=0.0, g2=None, s2=0.0, bn_state=No
     dev_t = scale.device
     nch = stats_chunks(B, xv.H, xv.W)
     part = torch.empty((nch, C, 2), dtype=torch.float32, device=dev_t)
+    if drop is not None:
+        d = _drop(drop)
+        check(l.stc_bn_bwd_reduce_drop(L.dtype_code(dt), B, xv, C, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), g1v,
+                                       float(s1), g2v, float(s2), ctypes.byref(d), ptr(part), nch, stream()),
+              "stc_bn_bwd_reduce_drop")
+        dgamma = _out1(dgamma, C, dev_t)
+        dbeta = _out1(dbeta, C, dev_t)
+        check(l.stc_bn_bwd_apply_drop(L.dtype_code(dt), B, xv, C, ptr(scale), ptr(shift), ptr(mean), ptr(rstd),
+                                      ptr(gamma), g1v, float(s1), g2v, float(s2), ctypes.byref(d), ptr(part), nch, dxv,
+                                      ptr(dgamma), ptr(dbeta), stream()), "stc_bn_bwd_apply_drop")
+        return dgamma, dbeta
     check(l.stc_bn_bwd_reduce(L.dtype_code(dt), B, xv, C, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), g1v,
                               float(s1), g2v, float(s2), ptr(part), nch, stream()), "stc_bn_bwd_reduce")
     dgamma = _out1(dgamma, C, dev_t)

@@ -84,6 +84,30 @@ def accumulate(acc, vals, d_out, weight=1.0):
         acc[k] = acc[k] + c.mean().double() * weight
 
 
+def dropout_trainer_seeds(base, rank, world):
+    """[G1's, G2's] dropout seed on data-parallel rank ``rank`` of ``world``, from the trainer's base seed: distinct
+    for every (generator, rank) of a run (ops.dropout_rank_seed).  Used at construction and at a checkpoint load."""
+    return [ops.dropout_rank_seed(base, rank, world, i) for i in range(2)]
+
+
+def dropout_checkpoint_entry(base, offsets):
+    """What a checkpoint keeps of the generators' dropout state: int64 [base seed (two's complement), G1's offset,
+    G2's offset].  The base seed, not rank 0's derived seeds: every rank re-derives its own at the load."""
+    base = int(base) & 0xFFFFFFFFFFFFFFFF
+    return torch.tensor([base - (1 << 64) if base >= (1 << 63) else base] + [int(o) for o in offsets],
+                        dtype=torch.int64)
+
+
+def dropout_from_checkpoint(entry, rank, world):
+    """(base seed, [(seed, offset) of G1, of G2]) for rank ``rank`` of ``world`` from dropout_checkpoint_entry's
+    tensor.  At the saving run's world size these are the seeds the ranks had, so the resumed run draws the
+    uninterrupted run's masks; at another world size the seeds are still distinct per (generator, rank), but the
+    shards and therefore the masks are another run's."""
+    base, *offsets = (int(v) for v in entry.tolist())
+    base &= 0xFFFFFFFFFFFFFFFF
+    return base, list(zip(dropout_trainer_seeds(base, rank, world), offsets))
+
+
 # loss type "normal": the G step's statistics-only real-input discriminator calls after the fake-input ones (their
 # running-statistics updates applied in the reference's order); False (A/B, tests): before them, as the reference
 LATE_STATS_CALLS = True
@@ -100,8 +124,12 @@ class STCGAN(object):
             raise RuntimeError("stcgan_amd.STCGAN needs a ROCm GPU")
         self.device = torch.device(self._device_of(args))
         ngf = getattr(args, "ngf", 64)
-        self.G1 = networks.get_generator(in_channels=3, out_channels=1, ngf=ngf)
-        self.G2 = networks.get_generator(in_channels=3 + 1, out_channels=3, ngf=ngf)
+        # args.use_dropout / args.droprate: pix2pix-style dropout after the up-norms above the bottleneck (train mode
+        # only; infer() ignores it), its masks drawn from each generator's device-resident {seed, offset}
+        self.use_dropout = bool(getattr(args, "use_dropout", False))
+        drop = dict(use_dropout=True, drop_rate=getattr(args, "droprate", 0.5)) if self.use_dropout else {}
+        self.G1 = networks.get_generator(in_channels=3, out_channels=1, ngf=ngf, **drop)
+        self.G2 = networks.get_generator(in_channels=3 + 1, out_channels=3, ngf=ngf, **drop)
         self.D1 = networks.get_discriminator(in_channels=3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False)
         self.D2 = networks.get_discriminator(in_channels=3 + 3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False)
         tasks = getattr(args, "tasks", ["train"])
@@ -118,6 +146,13 @@ class STCGAN(object):
             net.set_compute_dtype(dtype)
         # every rank starts from rank 0's weights (DataParallel replicates dev0's module)
         parallel.broadcast_state([self.G1, self.G2, self.D1, self.D2])
+        if self.use_dropout:
+            # a distinct mask stream per (generator, rank), derived from one base seed: args.dropout_seed, or torch's
+            base = getattr(args, "dropout_seed", None)
+            self.dropout_base = (torch.initial_seed() if base is None else int(base)) & 0xFFFFFFFFFFFFFFFF
+            for net, seed in zip((self.G1, self.G2),
+                                 dropout_trainer_seeds(self.dropout_base, parallel.rank(), parallel.world())):
+                net.set_dropout_seed(seed)
         self.start_epoch = 0
         self.optim_G = Adam(list(self.G1.parameters()) + list(self.G2.parameters()),
                             lr=args.lr_G, betas=(args.beta1, args.beta2))
@@ -644,14 +679,19 @@ class STCGAN(object):
 
     def save_checkpoint(self, epoch, path="./checkpoint.tar"):
         """Full training state (src/cgan.py:494-511): epoch, the four state_dicts, both
-        optimisers (Adam moments + step counts) and both LR schedulers; rank 0 only."""
+        optimisers (Adam moments + step counts) and both LR schedulers, plus, with use_dropout, the generators'
+        dropout base seed and offsets (key "dropout", dropout_checkpoint_entry); rank 0 only."""
         if parallel.rank() != 0:
             return
         mod = {k: (getattr(self, k).module if isinstance(getattr(self, k), nn.DataParallel) else getattr(self, k))
                for k in ("G1", "G2", "D1", "D2")}
-        torch.save({"epoch": epoch, **{k: m.state_dict() for k, m in mod.items()},
-                    "optim_G": self.optim_G.state_dict(), "optim_D": self.optim_D.state_dict(),
-                    "decay_G": self.decay_G.state_dict(), "decay_D": self.decay_D.state_dict()}, path)
+        ck = {"epoch": epoch, **{k: m.state_dict() for k, m in mod.items()},
+              "optim_G": self.optim_G.state_dict(), "optim_D": self.optim_D.state_dict(),
+              "decay_G": self.decay_G.state_dict(), "decay_D": self.decay_D.state_dict()}
+        if self.use_dropout:  # the base seed and each generator's offset: the ranks re-derive their seeds at the load
+            ck["dropout"] = dropout_checkpoint_entry(self.dropout_base,
+                                                     [mod[k].dropout_state()[1] for k in ("G1", "G2")])
+        torch.save(ck, path)
 
     def load_checkpoint(self, path="./checkpoint.tar"):
         """Resume from save_checkpoint (src/cgan.py:513-523; restores decay_G as well -- the
@@ -665,6 +705,10 @@ class STCGAN(object):
         self.optim_D.load_state_dict(ck["optim_D"])
         self.decay_G.load_state_dict(ck["decay_G"])
         self.decay_D.load_state_dict(ck["decay_D"])
+        if self.use_dropout and "dropout" in ck:  # (a checkpoint without it: the generators keep their state)
+            self.dropout_base, states = dropout_from_checkpoint(ck["dropout"], parallel.rank(), parallel.world())
+            for k, (seed, off) in zip(("G1", "G2"), states):
+                getattr(self, k).set_dropout_seed(seed, off)
 
     def init_weight(self, g1_weights=None, g2_weights=None, d1_weights=None, d2_weights=None):
         for name, path in (("G1", g1_weights), ("G2", g2_weights), ("D1", d1_weights), ("D2", d2_weights)):

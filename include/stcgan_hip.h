@@ -18,6 +18,7 @@
  *   stc_chan_stats / stc_bn_finalize               BatchNorm2d train/eval forward, STCGAN/networks.py:107,109,170,179
  *   stc_bn_bwd_reduce / stc_bn_bwd_apply            BatchNorm2d backward fused with LeakyReLU/ReLU backward
  *                    (with mean == NULL: LeakyReLU(0.2)/ReLU backward alone, networks.py:106,108,158)
+ *   stc_in_fwd / stc_in_bwd  InstanceNorm2d forward/backward fused with LeakyReLU/ReLU, STCGAN/networks.py:107,109,170,179 with norm_layer=nn.InstanceNorm2d
  *   stc_bn_apply_drop / stc_bn_bwd_*_drop / stc_dropout_*  nn.Dropout after the up-norm (use_dropout=True),
  *                    STCGAN/networks.py UnetSkipConnectionBlock: counter-based Philox masks, nothing stored
  *   stc_tanh_bias_bwd Tanh backward + outermost ConvT bias grad (networks.py:112-116)
@@ -289,6 +290,33 @@ int stc_bn_bwd_apply(int dtype, int B, stc_view x, int C,
                      stc_view g1, float slope1, stc_view g2, float slope2,
                      const float* part2, int nchunks,
                      stc_view dx, float* dgamma, float* dbeta, void* stream);
+
+/* ---- instance norm (norm_layer=nn.InstanceNorm2d) ------------------------------------------------------
+ * Statistics per (sample, channel) over the H x W extent of x, biased variance; the same computation in train
+ * and eval mode; no running statistics.  mean / rstd: fp32 [B][C].  gamma / beta: [C] or both NULL (1 and 0).
+ *   forward : n = (x - mean)*rstd*gamma + beta;  y1 = act(n, slope1), y2 = act(n, slope2) if y2.p != NULL,
+ *             written over apply_x: x itself or the top-left crop of its extent (same buffer and strides);
+ *             act and the rounding to the storage type as stc_bn_apply.
+ *   backward: n, xhat = (x - mean)*rstd recomputed from x;  dn = g1*act1'(n) + g2*act2'(n) (g1 / g2 optional,
+ *             over x's full extent);  per (b, c): s1 = sum dn, s2 = sum dn*xhat, P = H*W;
+ *             dx = gamma*rstd*(dn - s1/P - xhat*s2/P);  with gamma: dbeta[c] = sum_b s1, dgamma[c] = sum_b s2.
+ * Three plane-size regimes (stc_in_plan): tiny (a thread per (sample, channel vector), the plane in registers),
+ * resident (a workgroup per (sample, channel slab), the plane read once, one launch) and streamed (per-sample
+ * pixel chunks to fp32 partials in the workspace, merged in chunk order by the kernel that applies: two launches).
+ * Every sum runs in a fixed order (no atomics); the variance is a centred sum around the chunk's own mean.
+ * C must be a multiple of the 16-byte vector (4 fp32 / 8 bf16); a plane of one element is an error
+ * ("Expected more than 1 spatial element ...", torch's wording).  The workspace (stc_in_workspace bytes) serves
+ * the forward and the backward; the forward needs it only in the streamed regime, the backward also with gamma.
+ * out[4] = {regime (0 tiny, 1 resident, 2 streamed), channels per workgroup slab,
+ *           pixel chunks per sample, m = the longest chain of fp32 additions that forms one plane sum} */
+int     stc_in_plan(int dtype, int B, int H, int W, int C, int32_t* out);
+int64_t stc_in_workspace(int dtype, int B, int H, int W, int C);      /* bytes; forward and backward */
+int stc_in_fwd(int dtype, int B, stc_view x, int C, const float* gamma, const float* beta, float eps,
+               float* mean, float* rstd, stc_view apply_x, stc_view y1, float slope1, stc_view y2, float slope2,
+               void* ws, int64_t ws_bytes, void* stream);
+int stc_in_bwd(int dtype, int B, stc_view x, int C, const float* gamma, const float* beta,
+               const float* mean, const float* rstd, stc_view g1, float slope1, stc_view g2, float slope2,
+               stc_view dx, float* dgamma, float* dbeta, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- dropout of the U-Net generator (use_dropout=True) ----------------------------------------------
  * The reference appends nn.Dropout(0.5) after the up-norm of the num_downs - 5 blocks above the innermost one

@@ -90,6 +90,12 @@ _SIGS = {
                                  _vp]),
     "stc_bn_bwd_apply": (_i32, [_i32, _i32, View, _i32, _vp, _vp, _vp, _vp, _vp, View, _f32, View, _f32, _vp, _i32,
                                 View, _vp, _vp, _vp]),
+    "stc_in_plan": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp]),
+    "stc_in_workspace": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "stc_in_fwd": (_i32, [_i32, _i32, View, _i32, _vp, _vp, _f32, _vp, _vp, View, View, _f32, View, _f32, _vp, _i64,
+                          _vp]),
+    "stc_in_bwd": (_i32, [_i32, _i32, View, _i32, _vp, _vp, _vp, _vp, View, _f32, View, _f32, View, _vp, _vp, _vp,
+                          _i64, _vp]),
     "stc_dropout_next": (_i32, [_vp, _vp, _vp]),
     "stc_dropout_mask": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "stc_bn_apply_drop": (_i32, [_i32, _i32, View, _i32, _vp, _vp, View, _f32, View, _f32, _vp, _vp]),

@@ -22,6 +22,11 @@ channels, S[k] the block-k input resolution (S[1] = S[0]//2, S[k+1] = ceil(S[k]/
          use_dropout, train mode, the levels right above the innermost one: ReLU(BN_u(q_{k+1}) * keep/(1-p)), the
          mask a counter-based function of logical indices (GenPlan.drop, ops.dropout_next)
   y = tanh(convT_0(cr[0]) + bias), written NCHW fp32.
+
+norm_layer=nn.InstanceNorm2d (GenPlan.inorm / DiscPlan.inorm): the same buffers, with every
+"BN" above an instance norm -- a normed layer is the plain conv, then one ops.in_forward (statistics per sample over
+the stored raw output + the activation pass); its backward the input-gradient conv, then one ops.in_backward.  The
+BatchNorm path takes none of these calls.
 """
 import torch
 
@@ -243,6 +248,8 @@ class GenPlan:
         # {level k: p}: train-mode dropout on the output of BN_up[k] (the blocks right above the innermost one)
         self.drop = drop
         self.co = [c.out_channels for c in conv]
+        # which norm the network uses: BatchNorm2d, or InstanceNorm2d (affine or not)
+        self.inorm, self.affine = _norm_kind(list(bnd.values()) + list(bnu.values()))
         self.params = list(net.parameters())
 
 
@@ -257,6 +264,27 @@ def _sizes(H, W, Lv):
 def _pad2(S, k):
     """Padded size of resolution level k: 2 * S[k+1] (the extent a ConvT from level k+1 produces)."""
     return (2 * S[k + 1][0], 2 * S[k + 1][1])
+
+
+def _norm_kind(norms):
+    """(instance norm?, affine?) of a network's norm modules (networks.py admits one kind per network)."""
+    inorm = any(isinstance(m, torch.nn.InstanceNorm2d) for m in norms)
+    assert not inorm or all(type(m) is torch.nn.InstanceNorm2d for m in norms)
+    return inorm, inorm and any(m.weight is not None for m in norms)
+
+
+def _check_plane(B, C, h, w):
+    """torch's refusal of an instance norm over one spatial element (train and eval alike), before any launch."""
+    if h * w <= 1:
+        raise ValueError(f"Expected more than 1 spatial element when training, got input size "
+                         f"torch.Size([{B}, {C}, {h}, {w}])")
+
+
+def _conv_in_act(kind, B, xv, cin, w, cout, yv, dt, norm, apply_x, y1, s1, y2=None, s2=0.0):
+    """Conv -> InstanceNorm2d -> activation pass of ``apply_x`` into y1 [and y2]: the plain conv, then one
+    ops.in_forward (statistics of the stored raw output; the same in train and eval).  Returns (mean, rstd)."""
+    ops.conv(kind, B, xv, cin, w, cout, yv, dt)
+    return ops.in_forward(B, yv, cout, dt, norm, apply_x, y1, s1, y2, s2)
 
 
 def _conv_bn(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev):
@@ -299,6 +327,9 @@ def gen_forward(plan, sources, train, dt, cache, save):
     assert S[Lv][0] >= 1 and S[Lv][1] >= 1, "input too small for the generator depth"
     cin = sum(s.shape[1] for s in sources)
     assert cin == plan.in_c, f"generator expects {plan.in_c} input channels, got {cin}"
+    if plan.inorm:
+        for k in range(1, Lv - 1):
+            _check_plane(B, co[k], *S[k + 1])
     cin_pad = ops.pad_channels(cin, dt)
     xin = _nhwc(B, H, W, cin_pad, dt, dev)
     ops.gather(sources, xin, dt)
@@ -339,7 +370,11 @@ def gen_forward(plan, sources, train, dt, cache, save):
                      L.nhwc_view(cr[0], 0), 0.0)
     for k in range(1, Lv):
         wk = ops.packed(cache, plan.conv[k].weight, L.PACK_CONV_FWD, co[k], co[k - 1], dt)
-        if k <= Lv - 2:
+        if k <= Lv - 2 and plan.inorm:
+            rv = L.nhwc_view(rd[k])
+            st_d[k] = _conv_in_act(L.CONV_S2, B, L.nhwc_view(ad[k - 1]), co[k - 1], wk, co[k], rv, dt, plan.bnd[k], rv,
+                                   L.nhwc_view(ad[k]), LRELU, L.nhwc_view(cr[k], 0), 0.0)
+        elif k <= Lv - 2:
             rv = L.nhwc_view(rd[k])
             tab_d[k], st_d[k] = conv_bn_act(L.CONV_S2, L.nhwc_view(ad[k - 1]), co[k - 1], wk, co[k], rv, plan.bnd[k],
                                             rv, L.nhwc_view(ad[k]), LRELU, L.nhwc_view(cr[k], 0), 0.0)
@@ -350,6 +385,10 @@ def gen_forward(plan, sources, train, dt, cache, save):
     for k in range(Lv - 1, 0, -1):
         wt = ops.packed(cache, plan.convT[k].weight, L.PACK_CONVT_FWD, co[k - 1], cin_t(k), dt)
         # statistics over the full ConvT extent (before the crop of an odd level)
+        if plan.inorm:
+            st_u[k] = _conv_in_act(L.CONVT_S2, B, L.nhwc_view(cr[k]), cin_t(k), wt, co[k - 1], L.nhwc_view(rq[k]), dt,
+                                   plan.bnu[k], L.nhwc_view(rq[k], 0, *S[k]), L.nhwc_view(cr[k - 1], co[k - 1]), 0.0)
+            continue
         tab_u[k], st_u[k] = conv_bn_act(L.CONVT_S2, L.nhwc_view(cr[k]), cin_t(k), wt, co[k - 1], L.nhwc_view(rq[k]),
                                         plan.bnu[k], L.nhwc_view(rq[k], 0, *S[k]), L.nhwc_view(cr[k - 1], co[k - 1]),
                                         0.0, drop=drop_of(k))
@@ -386,6 +425,10 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
 
     def dest(p):
         return W.dest(p) if need_w else None
+
+    def dest_opt(p):
+        """dest of an affine parameter that a norm layer may not have."""
+        return W.dest(p) if (need_w and p is not None) else None
 
     # ---- tanh + bias
     cp = ops.vec(dt)
@@ -424,10 +467,21 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
         # is fused into the conv that writes gcat[k] (channels C..2C -> BN channels 0..C).
         ah, aw = _pad2(S, k + 1)
         C = co[k]
-        mean, rstd = st_u[k + 1]
-        t = tab_u[k + 1]
         dq = _nhwc(B, ah, aw, C, dt, dev)
         bn = plan.bnu[k + 1]
+        if plan.inorm:
+            # instance norm: the unfused form -- the conv writes gcat[k], then one fused ReLU + norm backward
+            ops.conv(L.CONV_S2, B, dqv, cg, wd, cin_t, L.nhwc_view(gcat[k], 0, *S[k + 1]), dt)
+            if need_w:
+                W.done([plan.convT[k].weight], lane)
+            ops.in_backward(B, L.nhwc_view(rq[k + 1]), C, dt, L.nhwc_view(dq), bn, st_u[k + 1],
+                            g1=L.nhwc_view(gcat[k], C), s1=0.0, dgamma=dest_opt(bn.weight), dbeta=dest_opt(bn.bias))
+            if need_w and plan.affine:
+                W.done([bn.weight, bn.bias])
+            _trace("G", ("dq", k + 1), dq)
+            continue
+        mean, rstd = st_u[k + 1]
+        t = tab_u[k + 1]
         drop = drops.get(k + 1)
         if drop is not None:
             # a dropout level: the gradient reaches BN_up[k+1]'s output through the mask, g * [n > 0] * keep/(1-p).
@@ -502,6 +556,16 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
                                 s2=LRELU)
             if need_w:
                 W.done([plan.conv[k].weight], lane)
+        elif plan.inorm:  # the conv writes ga, then one fused ReLU / LeakyReLU + instance-norm backward
+            bn = plan.bnd[k - 1]
+            ops.conv(L.CONVT_S2, B, drv, co[k], wd, cprev, L.nhwc_view(ga), dt)
+            if need_w:
+                W.done([plan.conv[k].weight], lane)
+            ops.in_backward(B, xv, cprev, dt, L.nhwc_view(dr), bn, st_d[k - 1], g1=g1, s1=0.0,
+                            g2=L.nhwc_view(ga, 0, *S[k]), s2=LRELU, dgamma=dest_opt(bn.weight),
+                            dbeta=dest_opt(bn.bias))
+            if need_w and plan.affine:
+                W.done([bn.weight, bn.bias])
         else:  # BN reduction fused into the input-gradient conv that produces ga
             mean, rstd = st_d[k - 1]
             t = tab_d[k - 1]
@@ -528,9 +592,10 @@ class DiscPlan:
         self.net = net
         seq = net.model
         convs = [m for m in seq if isinstance(m, torch.nn.Conv2d)]
-        bns = [m for m in seq if isinstance(m, torch.nn.BatchNorm2d)]
+        bns = [m for m in seq if isinstance(m, (torch.nn.BatchNorm2d, torch.nn.InstanceNorm2d))]
         assert len(convs) == len(bns) + 2
         self.convs, self.bns = convs, bns
+        self.inorm, self.affine = _norm_kind(bns)
         self.n = len(convs)
         self.strides = [c.stride[0] for c in convs]
         self.in_c = convs[0].in_channels
@@ -550,6 +615,15 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
     B, _, H, W = sources[0].shape
     cin = sum(s.shape[1] for s in sources)
     assert cin == plan.in_c, f"discriminator expects {plan.in_c} input channels, got {cin}"
+    n = plan.n
+    if plan.inorm:
+        if stats_only:  # no running statistics to advance: nothing to do (the zero-element placeholder, as below)
+            return torch.empty((B, plan.convs[-1].out_channels, 0, 0), dtype=torch.float32, device=dev), None
+        hw = (H, W)
+        for i, cv in enumerate(plan.convs[:-1]):
+            hw = (_conv_out(hw[0], plan.strides[i]), _conv_out(hw[1], plan.strides[i]))
+            if i >= 1:
+                _check_plane(B, cv.out_channels, *hw)
     cin_pad = ops.pad_channels(cin, dt)
     # first-layer bias gradient for free: a constant-1 plane in the first padding channel (its packed weights
     # are zero) makes the weight gradient's tap (1,1) of that channel sum the output gradient over every pixel
@@ -565,7 +639,6 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
         ops.gather(list(sources) + ([_ones_plane(B, H, W, dev)] if bias_ch is not None else []), xin, dt)
         if key is not None:
             inputs[key] = xin
-    n = plan.n
     raw, act, dims, chans, tabs, stats = [xin], [xin], [(H, W)], [cin_pad], [None], [None]
     out = None
     for i, cv in enumerate(plan.convs):
@@ -586,7 +659,13 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
             break
         tab, st = None, None
         a = _nhwc(B, h, w, cout, dt, dev)
-        if i >= 1:  # conv -> BatchNorm -> LeakyReLU (networks.py:167-180); no conv bias there
+        if i >= 1 and plan.inorm:  # conv -> InstanceNorm -> LeakyReLU
+            assert cv.bias is None
+            o = _nhwc(B, h, w, cout, dt, dev)
+            ov = L.nhwc_view(o)
+            st = _conv_in_act(kind, B, L.nhwc_view(act[i]), chans[i], wp, cout, ov, dt, plan.bns[i - 1], ov,
+                              L.nhwc_view(a), LRELU)
+        elif i >= 1:  # conv -> BatchNorm -> LeakyReLU (networks.py:167-180); no conv bias there
             assert cv.bias is None
             o = _nhwc(B, h, w, cout, dt, dev)
             ov = L.nhwc_view(o)
@@ -687,7 +766,17 @@ def disc_backward(plan, saved, gout, dt, cache, need_src, W):
         gn = _nhwc(B, ph, pw, cin, dt, dev)
         _trace("D", ("ga", i), ga)
         xv = L.nhwc_view(raw[i])
-        if tabs[i] is None:  # (no BatchNorm: the LeakyReLU backward in the conv epilogue when it has one)
+        if plan.inorm and stats[i] is not None:  # the conv writes ga, then LeakyReLU + instance-norm backward
+            bn = plan.bns[i - 2]
+            ops.conv(dkind, B, gv, gch, wd, cin, L.nhwc_view(ga), dt)
+            if need_w:
+                W.done(own, lane)
+            ops.in_backward(B, xv, cin, dt, L.nhwc_view(gn), bn, stats[i], g1=L.nhwc_view(ga), s1=LRELU,
+                            dgamma=W.dest(bn.weight) if (need_w and plan.affine) else None,
+                            dbeta=W.dest(bn.bias) if (need_w and plan.affine) else None)
+            if need_w and plan.affine:
+                W.done([bn.weight, bn.bias])
+        elif tabs[i] is None:  # (no BatchNorm: the LeakyReLU backward in the conv epilogue when it has one)
             if TRACE is not None or not ops.conv_act_backward(dkind, B, gv, gch, wd, cin, L.nhwc_view(gn), dt, act_x=xv,
                                                               s_self=LRELU):
                 ops.conv(dkind, B, gv, gch, wd, cin, L.nhwc_view(ga), dt)

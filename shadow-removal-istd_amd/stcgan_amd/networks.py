@@ -7,6 +7,9 @@ layers inside the tree only hold parameters and buffers; ``forward`` of the
 network runs the whole network as hand-written HIP kernels
 (``engine.gen_forward`` / ``engine.disc_forward``) behind one autograd node.
 
+``norm_layer``: nn.BatchNorm2d (default), nn.InstanceNorm2d, or a functools.partial of nn.InstanceNorm2d with
+``affine`` and/or ``eps`` (instance statistics in train and eval mode; no buffers); anything else raises.
+
 Differences from the reference that a caller can observe: none in values
 (parity-tested; ``use_dropout=True`` draws its train-mode masks from a counter-based
 generator of its own, ``set_dropout_seed`` / ``dropout_state``, not torch's); odd spatial sizes follow the pad/crop generator of
@@ -50,6 +53,29 @@ def check_drop_rate(p):
     if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= float(p) < 1.0:
         raise ValueError(f"stcgan_amd: dropout probability must be a number with 0 <= p < 1, got {p!r}")
     return float(p)
+
+
+def check_norm_layer(norm_layer, use_dropout=False):
+    """'batch' for nn.BatchNorm2d, 'instance' for nn.InstanceNorm2d or a functools.partial of it (affine and/or eps);
+    NotImplementedError for anything else.  Decided from the constructed module, as the layers will be."""
+    if norm_layer is nn.BatchNorm2d:
+        return "batch"
+    name = getattr(getattr(norm_layer, "func", norm_layer), "__name__", repr(norm_layer))
+    try:
+        m = norm_layer(8)
+    except Exception:
+        m = None
+    if type(m) is not nn.InstanceNorm2d:
+        raise NotImplementedError(f"stcgan_amd: norm_layer {name if m is None else type(m).__name__} is not on the "
+                                  "ST-CGAN path (nn.BatchNorm2d, nn.InstanceNorm2d or a functools.partial of "
+                                  "nn.InstanceNorm2d with affine / eps)")
+    if m.track_running_stats:
+        raise NotImplementedError("stcgan_amd: nn.InstanceNorm2d with track_running_stats=True is not supported "
+                                  "(instance statistics only, in train and eval mode)")
+    if use_dropout:
+        raise NotImplementedError("stcgan_amd: use_dropout=True together with nn.InstanceNorm2d is not supported "
+                                  "(the dropout kernels are written against the BatchNorm per-channel tables)")
+    return "instance"
 
 
 class _HipNet(nn.Module):
@@ -128,8 +154,7 @@ class UnetGenerator(_HipNet):
         from the nn.Dropout modules when the launch plan is made (the first forward, and again after a module move):
         set_drop_rate changes it later; writing ``Dropout.p`` by hand does not reach an existing plan."""
         super().__init__()
-        if norm_layer is not nn.BatchNorm2d:
-            raise NotImplementedError("stcgan_amd: only nn.BatchNorm2d is on the ST-CGAN path")
+        self.norm_kind = check_norm_layer(norm_layer, use_dropout)
         p = check_drop_rate(0.5 if drop_rate is None else drop_rate)
         self._drop_state = None  # device int64 {seed, offset}: a plain attribute, the state_dict keys stay the reference's
         unet_block = UnetSkipConnectionBlock(ngf * 8, ngf * 8, input_nc=None, submodule=None,
@@ -241,8 +266,7 @@ class NLayerDiscriminator(_HipNet):
 
     def __init__(self, in_channels, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, use_sigmoid=False):
         super().__init__()
-        if norm_layer is not nn.BatchNorm2d:
-            raise NotImplementedError("stcgan_amd: only nn.BatchNorm2d is on the ST-CGAN path")
+        self.norm_kind = check_norm_layer(norm_layer)
         if use_sigmoid:
             raise NotImplementedError("stcgan_amd: use_sigmoid=True is not on the ST-CGAN path "
                                       "(STCGAN/stcgan.py:39,41)")

@@ -783,6 +783,58 @@ def bn_backward(B, xv, C, dt, dxv, g1=None, s1=0.0, g2=None, s2=0.0, bn_state=No
     return dgamma, dbeta
 
 
+def in_plan(B, H, W, C, dt):
+    """(regime 0 tiny / 1 resident / 2 streamed, channels per slab, pixel chunks per sample, m) of stc_in_plan."""
+    key = ("inp", B, H, W, C, dt)
+    r = _MEMO.get(key)
+    if r is None:
+        out = (ctypes.c_int32 * 4)()
+        check(lib().stc_in_plan(L.dtype_code(dt), B, H, W, C, out), "stc_in_plan")
+        r = _MEMO[key] = tuple(out)
+    return r
+
+
+def _in_ws(B, xv, C, dt, dev):
+    key = ("inw", B, xv.H, xv.W, C, dt)
+    nbytes = _MEMO.get(key)
+    if nbytes is None:
+        nbytes = lib().stc_in_workspace(L.dtype_code(dt), B, xv.H, xv.W, C)
+        check(0 if nbytes >= 0 else -1, "stc_in_workspace")
+        _MEMO[key] = nbytes
+    return _ws(nbytes, dev)
+
+
+def in_forward(B, xv, C, dt, norm, apply_x, y1, s1, y2=None, s2=0.0):
+    """Instance norm of x (statistics per sample and channel over xv's extent) + activation pass of ``apply_x``
+    (xv or its top-left crop) into y1 [and y2]; ``norm``: the nn.InstanceNorm2d (eps; weight / bias when affine).
+    Returns (mean, rstd), fp32 [B, C]."""
+    dev = xv._keep.device
+    mean = torch.empty((B, C), dtype=torch.float32, device=dev)
+    rstd = torch.empty((B, C), dtype=torch.float32, device=dev)
+    ws, nb = _in_ws(B, xv, C, dt, dev)
+    check(lib().stc_in_fwd(L.dtype_code(dt), B, xv, C, ptr(norm.weight), ptr(norm.bias), float(norm.eps), ptr(mean),
+                           ptr(rstd), apply_x, y1, float(s1), y2 if y2 is not None else L.NULL_VIEW, float(s2),
+                           ptr(ws), nb, stream()), "stc_in_fwd")
+    return mean, rstd
+
+
+def in_backward(B, xv, C, dt, dxv, norm, stats, g1=None, s1=0.0, g2=None, s2=0.0, dgamma=None, dbeta=None):
+    """Fused activation + instance-norm backward into dxv; ``stats`` = in_forward's (mean, rstd).  Returns
+    (dgamma, dbeta), (None, None) for a norm without affine parameters."""
+    dev = xv._keep.device
+    mean, rstd = stats
+    ws, nb = _in_ws(B, xv, C, dt, dev)
+    if norm.weight is not None:
+        dgamma = _out1(dgamma, C, dev)
+        dbeta = _out1(dbeta, C, dev)
+    else:
+        dgamma = dbeta = None
+    check(lib().stc_in_bwd(L.dtype_code(dt), B, xv, C, ptr(norm.weight), ptr(norm.bias), ptr(mean), ptr(rstd),
+                           g1 if g1 is not None else L.NULL_VIEW, float(s1), g2 if g2 is not None else L.NULL_VIEW,
+                           float(s2), dxv, ptr(dgamma), ptr(dbeta), ptr(ws), nb, stream()), "stc_in_bwd")
+    return dgamma, dbeta
+
+
 def chan_sum(B, xv, C, Cout, dt, device, out=None):
     nch = stats_chunks(B, xv.H, xv.W)
     part = torch.empty((nch, C), dtype=torch.float32, device=device)

@@ -128,10 +128,15 @@ class STCGAN(object):
         # only; infer() ignores it), its masks drawn from each generator's device-resident {seed, offset}
         self.use_dropout = bool(getattr(args, "use_dropout", False))
         drop = dict(use_dropout=True, drop_rate=getattr(args, "droprate", 0.5)) if self.use_dropout else {}
-        self.G1 = networks.get_generator(in_channels=3, out_channels=1, ngf=ngf, **drop)
-        self.G2 = networks.get_generator(in_channels=3 + 1, out_channels=3, ngf=ngf, **drop)
-        self.D1 = networks.get_discriminator(in_channels=3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False)
-        self.D2 = networks.get_discriminator(in_channels=3 + 3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False)
+        # args.norm: "batch" (default) or "instance" -- the norm_layer of all four networks
+        self.norm = getattr(args, "norm", "batch")
+        if self.norm not in ("batch", "instance"):
+            raise ValueError(f"stcgan_amd: args.norm must be 'batch' or 'instance', got {self.norm!r}")
+        nl = dict(norm_layer=torch.nn.InstanceNorm2d if self.norm == "instance" else torch.nn.BatchNorm2d)
+        self.G1 = networks.get_generator(in_channels=3, out_channels=1, ngf=ngf, **nl, **drop)
+        self.G2 = networks.get_generator(in_channels=3 + 1, out_channels=3, ngf=ngf, **nl, **drop)
+        self.D1 = networks.get_discriminator(in_channels=3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False, **nl)
+        self.D2 = networks.get_discriminator(in_channels=3 + 3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False, **nl)
         tasks = getattr(args, "tasks", ["train"])
         if "infer" in tasks and "train" not in tasks:
             assert args.load_weights_g1 is not None
@@ -464,8 +469,10 @@ class STCGAN(object):
                 # held back and applied after theirs, in the reference's order: real then fake per BatchNorm) -- the
                 # G step's critical path (D update -> fake-input forwards -> their input gradients -> G backward)
                 # no longer waits for two forwards whose outputs nothing reads
-                late = unused and LATE_STATS_CALLS
-                if not late:
+                # Instance norm has no running statistics: nothing can observe those calls, so they are not made
+                skip = unused and self.norm == "instance"
+                late = unused and LATE_STATS_CALLS and not skip
+                if not late and not skip:
                     self.D1.stats_only = self.D2.stats_only = unused
                     C1_real = self._on(l1, self.D1, [x, m])
                     C2_real = self._on(l2, self.D2, [x, m, y])

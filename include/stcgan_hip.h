@@ -25,6 +25,7 @@
  *   stc_gather_nchw / stc_scatter_nchw              torch.cat input concat (stcgan.py:219-227,269-272) / its backward
  *   stc_loss_fwd / stc_loss_bwd                     DataLoss (L1) and AdversarialLoss (MSE / BCE-with-logits), loss.py:14-26,59-86
  *   stc_adam_step    torch.optim.Adam                STCGAN/stcgan.py:60-65
+ *   stc_adam_pack_step[_ex] ... the same fused with the weight repack; _ex: weight_decay (Adam / AdamW), amsgrad
  *   stc_infer_output infer() output stage: x*0.5+0.5, cv.resize INTER_LINEAR, float2uint
  *                    (STCGAN/stcgan.py:355-377, STCGAN/utils.py:63-65)
  *   stc_istd_errors  ISTD evaluation: masked LAB RMSE/MAE sums + PSNR squared error (src/eval.py:41-139)
@@ -501,7 +502,8 @@ int stc_adam_elems_per_block(void);
 /* Adam fused with the weight repack (replaces stc_adam_step + stc_pack_weights after a step):
  * table = ntensors records of 24 int64
  *   {param*, grad*, exp_avg*, exp_avg_sq*, numel, first_block, kind, P, Q, q_tiles, npacks,
- *    npacks x {mode, out*, N_pad, C_pad, dtype}, padding}
+ *    npacks x {mode, out*, N_pad, C_pad, dtype}, padding}   (slot 21: max_exp_avg_sq* for the _ex calls with
+ *    amsgrad, zero otherwise; slots 22, 23 zero)
  * kind 0: a flat tensor, ceil(numel / 1024) blocks.  kind 1: a [P][Q][4][4] weight, one block per
  * 16 x 16 (p, q) tile (q_tiles = ceil(Q / 16)), whose updated values are also written to each of
  * its npacks (<= 2) packed operands exactly as stc_pack_weight(dtype, mode, ..., N_pad, C_pad)
@@ -527,6 +529,39 @@ int stc_adam_coef_dev(int64_t* step_dev, const double* lr_dev, const double* bc1
                       int tab_len, float* coef_dev, void* stream);
 int stc_adam_pack_apply(const int64_t* table, int ntensors, int64_t total_blocks, float lr, int step,
                         const float* coef_dev, float beta1, float beta2, float eps, void* stream);
+/* The options of torch.optim.Adam / AdamW inside the fused update (the _ex forms of the four calls above;
+ * opts == NULL or an all-zero struct: exactly the launch of the call without _ex).  Per element, in fp32,
+ * in the order of torch's _single_tensor_adam:
+ *   weight_decay != 0, decoupled == 0 (Adam):   g' = g + weight_decay * p
+ *   weight_decay != 0, decoupled == 1 (AdamW):  p  = p * c,  c = (float)(1 - (double)lr * weight_decay)
+ *   exp_avg, exp_avg_sq as without options (from g')
+ *   amsgrad == 1:  max_exp_avg_sq = max(max_exp_avg_sq, exp_avg_sq), which replaces exp_avg_sq in the
+ *                  denominator; its pointer is slot 21 of the 24-wide record (slots 22, 23 stay zero)
+ *   p += -(lr/bc1) * exp_avg / (sqrt(.)/sqrt(bc2) + eps); the packed operands receive this p.
+ * lr is the float the call receives (on the device path the double *lr_dev holds).  With the step count on
+ * the device c is formed there too -- stc_adam_pack_step_dev_ex / stc_adam_coef_dev_ex write it to
+ * coef_dev[2] -- so coef_dev is 4 floats for the _ex calls, and stc_adam_pack_apply_ex with a coef_dev reads
+ * the c that stc_adam_coef_dev_ex wrote with the same options.
+ * Checked before any launch: weight_decay >= 0 (and not NaN), decoupled and amsgrad 0 or 1.  The table is
+ * device memory: whoever fills it on the host checks slot 21 (optim.Adam does); in the kernel a record whose
+ * slot 21 is zero under amsgrad is left untouched rather than dereferenced.                              */
+typedef struct stc_adam_opts {
+  double weight_decay;
+  int32_t decoupled;
+  int32_t amsgrad;
+} stc_adam_opts;
+int stc_adam_pack_step_ex(const int64_t* table, int ntensors, int64_t total_blocks,
+                          float lr, float beta1, float beta2, float eps, int step, const stc_adam_opts* opts,
+                          void* stream);
+int stc_adam_pack_step_dev_ex(const int64_t* table, int ntensors, int64_t total_blocks, int64_t* step_dev,
+                              const double* lr_dev, const double* bc1_tab, const float* bc2s_tab, int tab_len,
+                              float* coef_dev, float beta1, float beta2, float eps, const stc_adam_opts* opts,
+                              void* stream);
+int stc_adam_coef_dev_ex(int64_t* step_dev, const double* lr_dev, const double* bc1_tab, const float* bc2s_tab,
+                         int tab_len, float* coef_dev, const stc_adam_opts* opts, void* stream);
+int stc_adam_pack_apply_ex(const int64_t* table, int ntensors, int64_t total_blocks, float lr, int step,
+                           const float* coef_dev, float beta1, float beta2, float eps, const stc_adam_opts* opts,
+                           void* stream);
 /* dst[e] += src[e] (fp32, numel[e] elements) for ntensors <= 16 tensors in one launch (host arrays of
  * device pointers).  Sums the weight gradients of two calls of one network inside one differentiated
  * graph -- the discriminators' real and fake calls, STCGAN/stcgan.py:215-227 -- which autograd would

@@ -50,6 +50,11 @@ class Dropout(ctypes.Structure):
                 ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
+class AdamOpts(ctypes.Structure):
+    """stc_adam_opts: weight decay (coupled, or decoupled as AdamW) and amsgrad of the fused Adam update."""
+    _fields_ = [("weight_decay", ctypes.c_double), ("decoupled", ctypes.c_int32), ("amsgrad", ctypes.c_int32)]
+
+
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 
 # name: (restype, argtypes)
@@ -122,6 +127,10 @@ _SIGS = {
     "stc_adam_pack_step_dev": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _f32, _f32, _f32, _vp]),
     "stc_adam_coef_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "stc_adam_pack_apply": (_i32, [_vp, _i32, _i64, _f32, _i32, _vp, _f32, _f32, _f32, _vp]),
+    "stc_adam_pack_step_ex": (_i32, [_vp, _i32, _i64, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
+    "stc_adam_pack_step_dev_ex": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _f32, _f32, _f32, _vp, _vp]),
+    "stc_adam_coef_dev_ex": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "stc_adam_pack_apply_ex": (_i32, [_vp, _i32, _i64, _f32, _i32, _vp, _f32, _f32, _f32, _vp, _vp]),
     "stc_grad_accumulate": (_i32, [_i32, _vp, _vp, _vp, _vp]),
     "stc_infer_output": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "stc_istd_errors_workspace": (_i64, [_i32, _i32, _i32]),

@@ -1,12 +1,31 @@
-"""Multi-tensor Adam on one HIP launch (replaces torch.optim.Adam of STCGAN/stcgan.py:60-65).
+"""Multi-tensor Adam / AdamW on one HIP launch (replaces torch.optim.Adam of STCGAN/stcgan.py:60-65).
 
 Same constructor and ``step()/zero_grad()/state_dict()`` surface as
-torch.optim.Adam for the options the reference uses (lr, betas, eps;
-weight_decay=0, amsgrad=False).  The pointer table lives on the device and is
-rebuilt only when a tensor moved; ``step()`` never synchronises.  The 4x4
-weights' packed GEMM operands (ops.packed) are rewritten in the same launch as
-the update (stc_adam_pack_step), so the next forward finds them fresh.
+torch.optim.Adam / torch.optim.AdamW: lr, betas, eps, ``weight_decay``
+(coupled L2 in ``Adam``, decoupled in ``AdamW`` or with
+``decoupled_weight_decay=True``) and ``amsgrad``, per parameter group, with
+torch's ``param_groups`` keys and state keys (``max_exp_avg_sq``), so a state
+dict moves between the two in both directions.  ``foreach``, ``fused`` and
+``capturable`` are accepted and ignored (there is one implementation);
+``maximize`` and ``differentiable`` are not supported.  The pointer table lives
+on the device and is rebuilt only when a tensor moved; ``step()`` never
+synchronises.  The 4x4 weights' packed GEMM operands (ops.packed) are rewritten
+in the same launch as the update (stc_adam_pack_step), so the next forward
+finds them fresh -- with every option: decay and amsgrad are compile-time
+variants of that one kernel (stc_adam_pack_step_ex), on all four step paths
+(general, steady state, per-bucket overlap, device-resident step count).  A
+group with weight_decay == 0 and amsgrad off makes exactly the launch without
+options.
+
+weight_decay, decoupled_weight_decay and amsgrad are read from the group at
+every eager step (amsgrad switched on later, or a checkpoint saved without
+``max_exp_avg_sq``: the buffer is created as zeros at the next step).  A
+captured graph keeps the values of capture time, as it keeps betas and eps;
+only lr (sync_lr) -- and with it the decoupled decay factor 1 - lr * weight_decay,
+formed on the device -- and the step count follow later changes.
 """
+import ctypes
+
 import torch
 
 from . import _lib as L
@@ -16,10 +35,27 @@ from ._lib import check, lib, ptr, stream
 
 
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False):
-        if weight_decay != 0 or amsgrad:
-            raise NotImplementedError("stcgan_amd Adam: weight_decay/amsgrad are not on the ST-CGAN path")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False))
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *,
+                 foreach=None, maximize=False, capturable=False, differentiable=False, fused=None,
+                 decoupled_weight_decay=False):
+        if isinstance(lr, torch.Tensor) or any(isinstance(b, torch.Tensor) for b in betas):
+            raise NotImplementedError("stcgan_amd Adam: tensor-valued lr / betas are not supported")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if maximize or differentiable:
+            raise NotImplementedError("stcgan_amd Adam: maximize / differentiable are not supported")
+        # (foreach, fused, capturable: accepted for torch's signature and carried in the group; one implementation)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
+                                      maximize=False, foreach=foreach, capturable=capturable, differentiable=False,
+                                      fused=fused, decoupled_weight_decay=decoupled_weight_decay))
         self._epb = None
         self.fuse_pack = True  # False: update only (the packed operands are then refreshed lazily)
         self._dev = None  # device-resident step counts (device_step), per group
@@ -53,6 +89,30 @@ class Adam(torch.optim.Optimizer):
             self._tables = {}   # (group, step) -> (pointer key, device table, blocks)
             self._fast = {}     # group -> the last step's table and per-parameter records (see _fast_step)
 
+    @staticmethod
+    def _options(group):
+        """(stc_adam_opts or None, amsgrad) of a group, read at every step.  None -- no decay to apply and no
+        amsgrad -- takes the calls without options."""
+        wd = float(group.get("weight_decay", 0))
+        ams = bool(group.get("amsgrad", False))
+        if group.get("maximize", False) or group.get("differentiable", False):
+            raise NotImplementedError("stcgan_amd Adam: maximize / differentiable are not supported")
+        if not wd >= 0.0:
+            raise ValueError(f"Invalid weight_decay value: {wd}")
+        if wd == 0.0 and not ams:
+            return None, False
+        return L.AdamOpts(wd, int(bool(group.get("decoupled_weight_decay", False))), int(ams)), ams
+
+    def _pack_step(self, table, n, blocks, group, step, opts):
+        b1, b2 = group["betas"]
+        if opts is None:
+            check(lib().stc_adam_pack_step(ptr(table), n, blocks, float(group["lr"]), float(b1), float(b2),
+                                           float(group["eps"]), int(step), stream()), "stc_adam_pack_step")
+        else:
+            check(lib().stc_adam_pack_step_ex(ptr(table), n, blocks, float(group["lr"]), float(b1), float(b2),
+                                              float(group["eps"]), int(step), ctypes.byref(opts), stream()),
+                  "stc_adam_pack_step_ex")
+
     def _full_step(self, gi, group, skip=()):
         """The general path (first steps, moved tensors, new packed operands); ``skip``: parameters already
         updated this step (by overlap), left out.  With device-resident step counts (device_step) the host
@@ -60,7 +120,7 @@ class Adam(torch.optim.Optimizer):
         is set to the count this step reaches, so the next steady-state step (or replay) continues from it."""
         if self._dev is not None and gi in self._dev:
             self._pull_device_steps(gi, skip)
-        b1, b2 = group["betas"]
+        opts, ams = self._options(group)
         # group params by step count (all equal in practice).  The step count is mirrored in a
         # Python int (no per-parameter tensor op / .item() on the host path), and the state's
         # "step" tensors are advanced with one foreach call.
@@ -77,6 +137,8 @@ class Adam(torch.optim.Optimizer):
                 st["step"] = torch.tensor(0.0)
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if ams and "max_exp_avg_sq" not in st:  # (also: amsgrad switched on later, a checkpoint without it)
+                st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             mirror = self._steps.get(id(p))
             n = mirror[1] + 1 if mirror is not None and mirror[0] is st["step"] else int(st["step"].item()) + 1
             self._steps[id(p)] = (st["step"], n)
@@ -85,7 +147,7 @@ class Adam(torch.optim.Optimizer):
         if step_tensors:
             torch._foreach_add_(step_tensors, 1.0)
         for step, plist in by_step.items():
-            recs = [self._record(p) for p in plist]
+            recs = [self._record(p, ams) for p in plist]
             key = tuple(r[0] for r in recs)
             cached = self._tables.get(gi)
             if cached is not None and cached[0] == key:
@@ -101,9 +163,7 @@ class Adam(torch.optim.Optimizer):
                 # host until the GPU has drained everything queued before it (one full step)
                 table = torch.tensor(rows, dtype=torch.int64).pin_memory().to(plist[0].device, non_blocking=True)
                 self._tables[gi] = (key, table, blocks)
-            check(lib().stc_adam_pack_step(ptr(table), len(key), blocks, float(group["lr"]), float(b1),
-                                           float(b2), float(group["eps"]), int(step), stream()),
-                  "stc_adam_pack_step")
+            self._pack_step(table, len(key), blocks, group, step, opts)
             ops.bump(plist)
             for p, (_, _, targets) in zip(plist, recs):  # the packed operands written above are current
                 ver = ops.pack_version(p)
@@ -115,13 +175,13 @@ class Adam(torch.optim.Optimizer):
         self._fast.pop(gi, None)
         if len(by_step) == 1 and not skip:
             (step, plist), = by_step.items()
-            recs = [self._record(p) for p in plist]
+            recs = [self._record(p, ams) for p in plist]
             self._fast[gi] = dict(
                 key=tuple((id(p), p.data_ptr(), p.grad.data_ptr()) for p in plist), plist=plist,
                 rows=[list(r[0]) for r in recs], table=self._tables[gi][1], blocks=self._tables[gi][2],
                 targets=[r[2] for r in recs], step=step, epoch=ops.PACK_EPOCH,
                 step_tensors=[self.state[p]["step"] for p in plist],
-                index={id(p): i for i, p in enumerate(plist)}, subs={})
+                index={id(p): i for i, p in enumerate(plist)}, subs={}, ams=ams)
             f = self._fast[gi]
             f["tables"] = {f["key"]: (f["table"], f["blocks"])}
 
@@ -132,6 +192,9 @@ class Adam(torch.optim.Optimizer):
         read (usually unchanged: the table is then reused as is).  Returns False to take the full path."""
         f = self._fast.get(gi)
         if f is None or f["epoch"] != ops.PACK_EPOCH:
+            return False
+        opts, ams = self._options(group)
+        if ams != f["ams"]:  # amsgrad switched: the records gain or lose max_exp_avg_sq
             return False
         plist = f["plist"]
         key = []
@@ -169,12 +232,18 @@ class Adam(torch.optim.Optimizer):
         torch._foreach_add_(f["step_tensors"], 1.0)
         if self._dev is not None:
             d = self._dev_state(gi, group, f["step"], plist[0].device)
-            check(lib().stc_adam_pack_step_dev(ptr(f["table"]), len(plist), f["blocks"], ptr(d["step"]), ptr(d["lr_dev"]),
-                                               ptr(d["bc1"]), ptr(d["bc2s"]), d["tab_len"], ptr(d["coef"]), float(b1),
-                                               float(b2), float(group["eps"]), stream()), "stc_adam_pack_step_dev")
+            if opts is None:
+                check(lib().stc_adam_pack_step_dev(ptr(f["table"]), len(plist), f["blocks"], ptr(d["step"]),
+                                                   ptr(d["lr_dev"]), ptr(d["bc1"]), ptr(d["bc2s"]), d["tab_len"],
+                                                   ptr(d["coef"]), float(b1), float(b2), float(group["eps"]),
+                                                   stream()), "stc_adam_pack_step_dev")
+            else:
+                check(lib().stc_adam_pack_step_dev_ex(ptr(f["table"]), len(plist), f["blocks"], ptr(d["step"]),
+                                                      ptr(d["lr_dev"]), ptr(d["bc1"]), ptr(d["bc2s"]), d["tab_len"],
+                                                      ptr(d["coef"]), float(b1), float(b2), float(group["eps"]),
+                                                      ctypes.byref(opts), stream()), "stc_adam_pack_step_dev_ex")
         else:
-            check(lib().stc_adam_pack_step(ptr(f["table"]), len(plist), f["blocks"], float(group["lr"]), float(b1),
-                                           float(b2), float(group["eps"]), step, stream()), "stc_adam_pack_step")
+            self._pack_step(f["table"], len(plist), f["blocks"], group, step, opts)
         ops.bump(plist)
         for p, targets, st in zip(plist, f["targets"], f["step_tensors"]):
             self._steps[id(p)] = (st, step)
@@ -228,7 +297,7 @@ class Adam(torch.optim.Optimizer):
 
     def _launch_subset(self, gi, ps, stream, work):
         f = self._fast.get(gi)
-        if f is None or f["epoch"] != ops.PACK_EPOCH:
+        if f is None or f["epoch"] != ops.PACK_EPOCH or self._options(self.param_groups[gi])[1] != f["ams"]:
             return
         done = self._ov_done.get(gi, {})
         sel = []
@@ -260,16 +329,27 @@ class Adam(torch.optim.Optimizer):
         """One table launch of this step's update of group ``gi`` on the current stream."""
         group = self.param_groups[gi]
         b1, b2 = group["betas"]
+        opts, _ = self._options(group)
         coef = None
         if self._dev is not None:
             d = self._dev_state(gi, group, f["step"], f["plist"][0].device)
             if gi not in self._ov_coef:  # the device step count advances once per step
-                check(lib().stc_adam_coef_dev(ptr(d["step"]), ptr(d["lr_dev"]), ptr(d["bc1"]), ptr(d["bc2s"]),
-                                              d["tab_len"], ptr(d["coef"]), stream()), "stc_adam_coef_dev")
+                if opts is None:
+                    check(lib().stc_adam_coef_dev(ptr(d["step"]), ptr(d["lr_dev"]), ptr(d["bc1"]), ptr(d["bc2s"]),
+                                                  d["tab_len"], ptr(d["coef"]), stream()), "stc_adam_coef_dev")
+                else:
+                    check(lib().stc_adam_coef_dev_ex(ptr(d["step"]), ptr(d["lr_dev"]), ptr(d["bc1"]), ptr(d["bc2s"]),
+                                                     d["tab_len"], ptr(d["coef"]), ctypes.byref(opts), stream()),
+                          "stc_adam_coef_dev_ex")
                 self._ov_coef.add(gi)
             coef = ptr(d["coef"])
-        check(lib().stc_adam_pack_apply(ptr(table), n, blocks, float(group["lr"]), f["step"] + 1, coef, float(b1),
-                                        float(b2), float(group["eps"]), stream()), "stc_adam_pack_apply")
+        if opts is None:
+            check(lib().stc_adam_pack_apply(ptr(table), n, blocks, float(group["lr"]), f["step"] + 1, coef, float(b1),
+                                            float(b2), float(group["eps"]), stream()), "stc_adam_pack_apply")
+        else:
+            check(lib().stc_adam_pack_apply_ex(ptr(table), n, blocks, float(group["lr"]), f["step"] + 1, coef,
+                                               float(b1), float(b2), float(group["eps"]), ctypes.byref(opts),
+                                               stream()), "stc_adam_pack_apply_ex")
 
     def _finish_overlap(self, gi, group, done):
         """step() of a group part of which overlap() already updated this step."""
@@ -277,7 +357,8 @@ class Adam(torch.optim.Optimizer):
         plist = f["plist"]
         torch.cuda.current_stream(plist[0].device).wait_stream(self._ov_stream)
         with_grad = [p for p in group["params"] if p.grad is not None]
-        ok = f["epoch"] == ops.PACK_EPOCH and len(with_grad) == len(plist)
+        ok = (f["epoch"] == ops.PACK_EPOCH and len(with_grad) == len(plist)
+              and self._options(group)[1] == f["ams"])
         rest = []
         for p in with_grad:
             i = f["index"].get(id(p))
@@ -351,7 +432,8 @@ class Adam(torch.optim.Optimizer):
                      bc2s=torch.tensor(np.asarray(bc2s, dtype=np.float64).astype(np.float32), device=device),
                      step=torch.tensor([int(host_step)], dtype=torch.int64, device=device),
                      lr_dev=torch.zeros(1, dtype=torch.float64, device=device),
-                     coef=torch.zeros(2, dtype=torch.float32, device=device))
+                     # lr / bc1, sqrt(bc2), the decoupled decay factor 1 - lr * weight_decay, one spare
+                     coef=torch.zeros(4, dtype=torch.float32, device=device))
             self._dev[gi] = d
         if host_step + 1 >= d["tab_len"]:
             raise RuntimeError("stcgan_amd Adam: device step table exhausted; device_step(tab_len=...) larger")
@@ -430,18 +512,22 @@ class Adam(torch.optim.Optimizer):
         self._ov_done = {}
         # the moment buffers keep their storage: a captured graph (STCGAN.capture) and its pointer tables hold
         # their addresses, so the loaded values are copied into them rather than swapped in as new tensors
-        held = {id(p): (p, {k: v for k, v in self.state[p].items() if k in ("exp_avg", "exp_avg_sq")})
+        held = {id(p): (p, {k: v for k, v in self.state[p].items()
+                            if k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")})
                 for g in self.param_groups for p in g["params"] if p in self.state}
         out = super().load_state_dict(state_dict)
+        ams_of = {id(p): bool(g.get("amsgrad", False)) for g in self.param_groups for p in g["params"]}
         for p, old in held.values():
             st = self.state.get(p)
-            if st is None:
+            if not st:
                 continue
             for k, t in old.items():
                 new = st.get(k)
                 if new is not None and new is not t and new.shape == t.shape:
                     t.copy_(new)
                     st[k] = t
+                elif new is None and k == "max_exp_avg_sq" and ams_of[id(p)]:
+                    st[k] = t.zero_()  # a state saved without it: zeros, in the buffer the tables hold
         # device-resident counts (device_step): the loaded state's; the counter tensors are kept (a captured
         # graph holds them), the next step takes the general path and writes them
         if self._dev:
@@ -451,19 +537,35 @@ class Adam(torch.optim.Optimizer):
                     d["step"].fill_(int(st[0].item()))
         return out
 
-    def _record(self, p):
-        """(table row without first_block, blocks, packed targets) of one parameter."""
+    def _record(self, p, ams=False):
+        """(table row without first_block, blocks, packed targets) of one parameter; ``ams``: slot 21 of the
+        record (20 here, first_block is inserted later) holds max_exp_avg_sq."""
         st = self.state[p]
         head = (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel())
+        vmax = 0
+        if ams:
+            vmax = st["max_exp_avg_sq"].data_ptr()
+            if vmax == 0 and p.numel():
+                raise RuntimeError("stcgan_amd Adam: amsgrad without a max_exp_avg_sq buffer")
         is_w = self.fuse_pack and p.dim() == 4 and tuple(p.shape[2:]) == (4, 4)
         targets = ops.pack_targets(p)[:2] if is_w else []
         if not targets:
-            return head + (0, 0, 0, 0, 0) + (0,) * 13, (p.numel() + 1023) // 1024, []
+            return head + (0, 0, 0, 0, 0) + (0,) * 10 + (vmax, 0, 0), (p.numel() + 1023) // 1024, []
         P, Q = p.shape[0], p.shape[1]
         qt = (Q + 15) // 16
         packs = ()
         for (_, _, mode, out, n_pad, c_pad, dt) in targets:
             packs += (mode, out.data_ptr(), n_pad, c_pad, L.dtype_code(dt))
         packs += (0,) * (10 - len(packs))
-        return (head + (1, P, Q, qt, len(targets)) + packs + (0,) * 3, ((P + 15) // 16) * qt,
+        return (head + (1, P, Q, qt, len(targets)) + packs + (vmax, 0, 0), ((P + 15) // 16) * qt,
                 [(t[0], t[1], t[3]) for t in targets])
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW: Adam with decoupled weight decay (p *= 1 - lr * weight_decay before the update)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *,
+                 maximize=False, foreach=None, capturable=False, differentiable=False, fused=None):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize,
+                         capturable=capturable, differentiable=differentiable, fused=fused,
+                         decoupled_weight_decay=True)

@@ -33,7 +33,7 @@ from . import ops
 from . import networks
 from . import parallel
 from .loss import AdversarialLoss, DataLoss, d_objective, d_term_grad, g_objective
-from .optim import Adam
+from .optim import Adam, AdamW
 
 
 class SyntheticTriplets:
@@ -133,6 +133,17 @@ class STCGAN(object):
         if self.norm not in ("batch", "instance"):
             raise ValueError(f"stcgan_amd: args.norm must be 'batch' or 'instance', got {self.norm!r}")
         nl = dict(norm_layer=torch.nn.InstanceNorm2d if self.norm == "instance" else torch.nn.BatchNorm2d)
+        # args.optimizer: "adam" (default) or "adamw"; args.weight_decay (0) and args.amsgrad (False) go to both
+        # optimisers -- coupled L2 decay with "adam", decoupled with "adamw" (optim.Adam / optim.AdamW)
+        self.optimizer = getattr(args, "optimizer", "adam")
+        if self.optimizer not in ("adam", "adamw"):
+            raise ValueError(f"stcgan_amd: args.optimizer must be 'adam' or 'adamw', got {self.optimizer!r}")
+        weight_decay = float(getattr(args, "weight_decay", 0))
+        if not weight_decay >= 0.0:
+            raise ValueError(f"stcgan_amd: args.weight_decay must be >= 0, got {weight_decay!r}")
+        amsgrad = getattr(args, "amsgrad", False)
+        if not isinstance(amsgrad, (bool, int)) or amsgrad not in (0, 1):
+            raise ValueError(f"stcgan_amd: args.amsgrad must be a bool, got {amsgrad!r}")
         self.G1 = networks.get_generator(in_channels=3, out_channels=1, ngf=ngf, **nl, **drop)
         self.G2 = networks.get_generator(in_channels=3 + 1, out_channels=3, ngf=ngf, **nl, **drop)
         self.D1 = networks.get_discriminator(in_channels=3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False, **nl)
@@ -159,10 +170,10 @@ class STCGAN(object):
                                  dropout_trainer_seeds(self.dropout_base, parallel.rank(), parallel.world())):
                 net.set_dropout_seed(seed)
         self.start_epoch = 0
-        self.optim_G = Adam(list(self.G1.parameters()) + list(self.G2.parameters()),
-                            lr=args.lr_G, betas=(args.beta1, args.beta2))
-        self.optim_D = Adam(list(self.D1.parameters()) + list(self.D2.parameters()),
-                            lr=args.lr_D, betas=(args.beta1, args.beta2))
+        make_optim = AdamW if self.optimizer == "adamw" else Adam
+        okw = dict(betas=(args.beta1, args.beta2), weight_decay=weight_decay, amsgrad=bool(amsgrad))
+        self.optim_G = make_optim(list(self.G1.parameters()) + list(self.G2.parameters()), lr=args.lr_G, **okw)
+        self.optim_D = make_optim(list(self.D1.parameters()) + list(self.D2.parameters()), lr=args.lr_D, **okw)
         self.decay_G = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optim_G, cooldown=10, min_lr=1e-7, factor=0.8)
         self.decay_D = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optim_D, cooldown=10, min_lr=1e-7, factor=0.8)
         # each network's gradients live in one flat buffer (parallel.FlatGrads), cut into buckets that the

@@ -8,7 +8,9 @@ chunks, ragged N, channel-offset input and output views (the concat buffers), bi
 and the fused BatchNorm-backward sums of the epilogue, the automatic plan at the train step's sizes.
 Operands are bf16-exact, so the references differ by fp32 summation order and the final bf16 rounding only:
 1e-2 * max|ref| on outputs (as tests/test_gpu_igemm_bf16.py), 2e-3 on the statistics.  Against the im2col tile
-(a different but fixed K order) the outputs agree to the same bound.
+(a different but fixed K order) the outputs agree to the same bound.  These bounds cover real-valued summation
+error only; single wrong products, reads outside a view, the bf16 store's rounding and the statistics to one pixel
+are pinned bit-exactly, on these same cases and forced shapes, by tests/test_gpu_conv_exact.py.
 """
 import pytest
 import torch

@@ -24,6 +24,11 @@
  *   stc_tanh_bias_bwd Tanh backward + outermost ConvT bias grad (networks.py:112-116)
  *   stc_gather_nchw / stc_scatter_nchw              torch.cat input concat (stcgan.py:219-227,269-272) / its backward
  *   stc_loss_fwd / stc_loss_bwd                     DataLoss (L1) and AdversarialLoss (MSE / BCE-with-logits), loss.py:14-26,59-86
+ *   stc_conv3_fwd / stc_conv3_pack / stc_conv3_plan  Conv2d 3x3 s1 p1 (+ folded eval BatchNorm, ReLU) of the vgg19_bn
+ *                    features and its input gradient: VisualLoss, src/loss.py:29-56
+ *   stc_maxpool2_fwd / stc_maxpool2_bwd             MaxPool2d(2, 2) of the same Sequential
+ *   stc_vgg_norm_fwd / stc_vgg_norm_bwd             VisualLoss input normalisation (src/loss.py:46-50) and its backward
+ *   stc_feat_mse_fwd / stc_feat_mse_bwd             F.mse_loss between the two feature tensors (src/loss.py:52-56)
  *   stc_adam_step    torch.optim.Adam                STCGAN/stcgan.py:60-65
  *   stc_adam_pack_step[_ex] ... the same fused with the weight repack; _ex: weight_decay (Adam / AdamW), amsgrad
  *   stc_infer_output infer() output stage: x*0.5+0.5, cv.resize INTER_LINEAR, float2uint
@@ -416,6 +421,61 @@ int stc_loss_fwd(int kind, const float* p, const float* t, float c, int64_t n,
                  float* part, float* out, void* stream);
 int stc_loss_bwd(int kind, const float* p, const float* t, float c, int64_t n,
                  const float* gout, float* grad, void* stream);
+
+/* ---- VisualLoss: vgg19_bn features in bf16 (src/loss.py:29-56 of the reference's src/ line) -----------------
+ * An eval-mode vgg19_bn `features` prefix (Conv2d k3 s1 p1 [+ BatchNorm2d folded into the conv by the caller] + ReLU,
+ * MaxPool2d(2, 2)) on NHWC bf16 views with fp32 accumulation, and the MSE between the features of two images.
+ *
+ * stc_conv3_fwd: y[b, oy, ox, n] = act(sum_{ky, kx, c} x[b, oy + ky - 1, ox + kx - 1, c] * w[n][ky * 3 + kx][c] + bias[n])
+ *   (zero padding; bias fp32 or NULL; relu != 0: max(., 0)), rounded once to bf16; with mask.p != NULL the result is
+ *   multiplied by [mask[b, oy, ox, n] > 0] (the input gradient through the ReLU whose output is `mask`; no bias then).
+ *   w_packed: bf16 [Cout][9][Cin] from stc_conv3_pack -- its `fwd` output for the forward, its `dgrad` output (taps
+ *   flipped, ci / co swapped) with Cin / Cout exchanged for the input gradient.  Cin and Cout are multiples of 8 (a
+ *   3-channel image is stored as 8 channels, 5 of them zero, with zero weights); x, y, mask: one extent H x W >= 1,
+ *   cs = 1, 16-byte aligned pixels (channel-offset views of a wider buffer are fine); B*H*W < 2^24, the input extent
+ *   below 2 GiB.  One LDS-halo MFMA kernel (csrc/conv3_bf16.hip), fixed K order (32-channel chunk, ky, kx), no split,
+ *   no workspace: bit-identical from run to run and across streams.
+ * stc_conv3_plan: out[8] = {path (0: the halo kernel -- the only one), tile rows TH, tile columns TW (a block owns TH x TW
+ *   output pixels of one image: BM = TH*TW GEMM rows), BN, K chunk (channels per stage), K splits (1),
+ *   M tiles = B*ceil(H/TH)*ceil(W/TW), N tiles = ceil(Cout/BN)} for the same shape.
+ * stc_conv3_pack: n <= STC_CONV3_PACK_MAX layers in one launch; W: fp32 [Co][Ci][3][3] (torch layout);
+ *   fwd (nullable): bf16 [Co_pad][9][Ci_pad], fwd[n][t][c] = W[n][c][t]; dgrad (nullable): bf16 [Ci_pad][9][Co_pad],
+ *   dgrad[m][t][k] = W[k][m][8 - t]; round-to-nearest-even, padding entries zero.                               */
+#define STC_CONV3_PACK_MAX 16
+typedef struct {
+  const float* W;
+  void* fwd;
+  void* dgrad;
+  int32_t Co, Ci, Co_pad, Ci_pad;
+} stc_conv3_pack_desc;
+int stc_conv3_plan(int B, int H, int W, int Cin, int Cout, int32_t* out);
+int stc_conv3_fwd(int B, stc_view x, int Cin, const void* w_packed, int Cout, stc_view y, const float* bias, int relu,
+                  stc_view mask, void* stream);
+int stc_conv3_pack(int n, const stc_conv3_pack_desc* descs, void* stream);
+/* MaxPool2d(2, 2) (floor mode, no padding) on NHWC bf16, C % 8 == 0, x.H and x.W even; y / gy: x.H/2 x x.W/2.
+ * bwd: gx (x's extent, every element written) receives each window's gradient at its first maximal element in scan
+ * order (0,0), (0,1), (1,0), (1,1) -- torch's rule (a later element wins only when greater, or NaN) -- recomputed
+ * from the pool input x; no index tensor.                                                                        */
+int stc_maxpool2_fwd(int B, stc_view x, int C, stc_view y, void* stream);
+int stc_maxpool2_bwd(int B, stc_view x, int C, stc_view gy, stc_view gx, void* stream);
+/* fwd: dst[b, y, x, c] = ((src[b, c, y, x] * 0.5 + 0.5) - mean_c) / std_c for c < 3 (ImageNet mean 0.485, 0.456, 0.406
+ *   and std 0.229, 0.224, 0.225), evaluated in fp64 and rounded to fp32, then to bf16; channels 3..7 zero.  src: fp32
+ *   with element strides sb, sc, sh, sw >= 0 (0 for an expanded dimension); dst: NHWC bf16 view of 8 channels.
+ * bwd: dst[b][c][y][x] (fp32, contiguous [B][3][H][W]) = g[b, y, x, c] * (float)(0.5 / std_c).                    */
+int stc_vgg_norm_fwd(int B, int H, int W, const float* src, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
+                     stc_view dst, void* stream);
+int stc_vgg_norm_bwd(int B, int H, int W, stc_view g, float* dst, void* stream);
+/* MSE between two dense bf16 tensors of n elements (n % 8 == 0, 16-byte aligned).
+ * fwd: out[0] = sum (fp - ft)^2 / n: per 4096-element block an fp32 sum whose longest chain of additions is
+ *   stc_feat_mse_chain() (a thread's 16 elements in order, then an 8-level tree), the stc_feat_mse_parts(n) block
+ *   sums (the workspace `part`, floats) added in fp64 in a fixed order.
+ * bwd: g = bf16(gout[0] * 2 (fp - ft) / n) (gout: fp32 device scalar; the product in fp64, rounded to fp32, then to
+ *   bf16); relu_mask != 0: times [fp > 0] (fp is a ReLU output, or a max-pool of one).                           */
+int stc_feat_mse_parts(int64_t n);
+int stc_feat_mse_chain(void);
+int stc_feat_mse_fwd(const void* fp, const void* ft, int64_t n, float* part, float* out, void* stream);
+int stc_feat_mse_bwd(const void* fp, const void* ft, int64_t n, const float* gout, int relu_mask, void* g,
+                     void* stream);
 
 /* ---- inference output stage ---------------------------------------------------
  * src: generator output NCHW fp32 [B][C][H][W] (tanh range); dst: HWC uint8 [B][OH][OW][C],

@@ -44,6 +44,15 @@ class PackDesc(ctypes.Structure):
                 ("C_pad", ctypes.c_int32), ("pad_", ctypes.c_int32), ("W", ctypes.c_void_p), ("out", ctypes.c_void_p)]
 
 
+CONV3_PACK_MAX = 16
+
+
+class Conv3PackDesc(ctypes.Structure):
+    """stc_conv3_pack_desc: one 3x3 conv weight of a stc_conv3_pack launch."""
+    _fields_ = [("W", ctypes.c_void_p), ("fwd", ctypes.c_void_p), ("dgrad", ctypes.c_void_p), ("Co", ctypes.c_int32),
+                ("Ci", ctypes.c_int32), ("Co_pad", ctypes.c_int32), ("Ci_pad", ctypes.c_int32)]
+
+
 class Dropout(ctypes.Structure):
     """stc_dropout: one dropout level of one generator call (state: that call's device {seed, offset})."""
     _fields_ = [("state", ctypes.c_void_p), ("p", ctypes.c_double), ("level", ctypes.c_int32),
@@ -132,6 +141,17 @@ _SIGS = {
     "stc_adam_coef_dev_ex": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "stc_adam_pack_apply_ex": (_i32, [_vp, _i32, _i64, _f32, _i32, _vp, _f32, _f32, _f32, _vp, _vp]),
     "stc_grad_accumulate": (_i32, [_i32, _vp, _vp, _vp, _vp]),
+    "stc_conv3_plan": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp]),
+    "stc_conv3_fwd": (_i32, [_i32, View, _i32, _vp, _i32, View, _vp, _i32, View, _vp]),
+    "stc_conv3_pack": (_i32, [_i32, _vp, _vp]),
+    "stc_maxpool2_fwd": (_i32, [_i32, View, _i32, View, _vp]),
+    "stc_maxpool2_bwd": (_i32, [_i32, View, _i32, View, View, _vp]),
+    "stc_vgg_norm_fwd": (_i32, [_i32, _i32, _i32, _vp, _i64, _i64, _i64, _i64, View, _vp]),
+    "stc_vgg_norm_bwd": (_i32, [_i32, _i32, _i32, View, _vp, _vp]),
+    "stc_feat_mse_parts": (_i32, [_i64]),
+    "stc_feat_mse_chain": (_i32, []),
+    "stc_feat_mse_fwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "stc_feat_mse_bwd": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp]),
     "stc_infer_output": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "stc_istd_errors_workspace": (_i64, [_i32, _i32, _i32]),
     "stc_istd_errors": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),

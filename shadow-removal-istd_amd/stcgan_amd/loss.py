@@ -2,7 +2,8 @@
 
 DataLoss (STCGAN/loss.py:14-26) and AdversarialLoss (STCGAN/loss.py:59-86) run as
 HIP reduction kernels (deterministic two-level sums) with hand-written gradients.
-VisualLoss and SoftAdapt are not on the path.
+VisualLoss (src/loss.py:29-56) runs an eval-mode vgg19_bn feature chain in bf16 on the
+HIP 3x3 MFMA conv kernels.  SoftAdapt is not on the path.
 """
 import ctypes
 
@@ -230,3 +231,234 @@ class RelativisticAdversarialLoss(nn.Module):
         if D_loss:  # SGAN
             return (self.cal_loss(C_real, real) + self.cal_loss(C_fake, fake)) * 0.5
         return self.cal_loss(C_fake, real)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# VisualLoss (src/loss.py:29-56 of the reference's src/ line): MSE between the features of an eval-mode vgg19_bn.
+# bf16 activations and weights, fp32 accumulation, fp32 loss sums -- also under the fp32-parity trainer.
+# Rounding points, in order: the normalised input; the folded weights; each conv+bias+ReLU output; each pool output
+# (exact); g = gout * 2 (f_p - f_t) / N; each input-gradient conv output (after the ReLU mask).  The fp32 gradient of
+# the input is g0 * 0.5 / std_c.
+
+# When a dict: one VisualLoss call records every tensor it stored (tests; like engine.TRACE).  forward: "input" (the
+# normalised pred | target batch, NHWC bf16 [2B, H, W, 8]), "items" (("conv", layer index) / ("pool",) per module
+# group), "acts" (each item's output, [2B, ...]), "packed" ([(fwd, dgrad)] per conv as packed), "biases", "loss";
+# backward: "g_feat" (the MSE gradient), "grads" (the gradient each item passes to its input, in item order),
+# "g_input" (fp32 [B, 3, H, W]).
+TRACE = None
+
+_VGG19_WIDTHS = (64, 128, 256, 512)
+
+
+def vgg19_bn_features(state_dict=None, upto=40, widths=_VGG19_WIDTHS):
+    """torchvision's ``vgg19_bn().features[:upto]`` from plain torch.nn (cfg E: convs at 0, 3, 7, 10, 14, 17, 20, 23,
+    27, 30, 33, 36, ..., BatchNorm at +1, ReLU at +2, pools at 6, 13, 26, 39, 52; [:40] ends with pool4).
+    state_dict: a torchvision vgg19_bn state_dict -- its ``features.N.*`` entries with N < upto are loaded, the
+    ``classifier.*`` and later entries ignored.  widths: the four block widths (block 5 has the fourth), for a
+    scaled-down network of the same shape."""
+    w1, w2, w3, w4 = widths
+    cfg = [w1, w1, "M", w2, w2, "M", w3, w3, w3, w3, "M", w4, w4, w4, w4, "M", w4, w4, w4, w4, "M"]
+    mods, cin = [], 3
+    for v in cfg:
+        if v == "M":
+            mods.append(nn.MaxPool2d(kernel_size=2, stride=2))
+        else:
+            mods += [nn.Conv2d(cin, v, kernel_size=3, padding=1), nn.BatchNorm2d(v), nn.ReLU(inplace=True)]
+            cin = v
+    seq = nn.Sequential(*mods[:upto])
+    if state_dict is not None:
+        own = seq.state_dict()
+        sub = {}
+        for k, v in state_dict.items():
+            if k.startswith("features.") and k[len("features."):] in own:
+                sub[k[len("features."):]] = v
+        seq.load_state_dict(sub, strict=True)
+    return seq.requires_grad_(False).eval()
+
+
+def _pad8(c):
+    return -(-c // 8) * 8
+
+
+def _parse_features(features):
+    """The Sequential grammar: (Conv2d k3 s1 p1 zeros [BatchNorm2d] ReLU | MaxPool2d(2, 2))*."""
+    if not isinstance(features, nn.Sequential):
+        raise NotImplementedError(f"stcgan_amd VisualLoss: features must be an nn.Sequential, got {type(features).__name__}")
+    mods = list(features)
+    items, i, cin = [], 0, 3
+
+    def two(v):
+        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+    while i < len(mods):
+        m = mods[i]
+        if isinstance(m, nn.MaxPool2d):
+            if two(m.kernel_size) != (2, 2) or two(m.stride) != (2, 2) or two(m.padding) != (0, 0) \
+                    or two(m.dilation) != (1, 1) or m.ceil_mode or m.return_indices:
+                raise NotImplementedError(f"stcgan_amd VisualLoss: only MaxPool2d(2, 2) is on the path, got {m}")
+            items.append(("pool",))
+            i += 1
+            continue
+        if isinstance(m, nn.Conv2d):
+            if m.kernel_size != (3, 3) or m.stride != (1, 1) or m.padding != (1, 1) or m.dilation != (1, 1) \
+                    or m.groups != 1 or m.padding_mode != "zeros" or m.in_channels != cin or m.out_channels % 8 != 0:
+                raise NotImplementedError("stcgan_amd VisualLoss: only Conv2d(k=3, s=1, p=1, zero padding) with "
+                                          f"{cin} input channels and a multiple of 8 output channels is on the path, got {m}")
+            bn = None
+            j = i + 1
+            if j < len(mods) and isinstance(mods[j], nn.BatchNorm2d):
+                bn = mods[j]
+                if not bn.track_running_stats or bn.running_mean is None:
+                    raise NotImplementedError(f"stcgan_amd VisualLoss: BatchNorm2d needs running statistics, got {bn}")
+                j += 1
+            if j >= len(mods) or not isinstance(mods[j], nn.ReLU):
+                got = mods[j] if j < len(mods) else "the end of the Sequential"
+                raise NotImplementedError(f"stcgan_amd VisualLoss: a ReLU must follow {m}, got {got}")
+            items.append(("conv", m, bn))
+            cin = m.out_channels
+            i = j + 1
+            continue
+        raise NotImplementedError(f"stcgan_amd VisualLoss: module {i} is not on the path: {m}")
+    if not any(it[0] == "conv" for it in items):
+        raise NotImplementedError("stcgan_amd VisualLoss: features has no Conv2d")
+    return items
+
+
+class _VisualFn(torch.autograd.Function):
+    """The whole loss as one node: normalise, the feature chain on the pred | target batch, the MSE."""
+
+    @staticmethod
+    def forward(ctx, mod, y_pred, y_target):
+        from . import ops
+        tr = TRACE if isinstance(TRACE, dict) else None
+        if y_pred.dtype != torch.float32 or y_target.dtype != torch.float32 or not y_pred.is_cuda \
+                or not y_target.is_cuda:
+            raise TypeError("stcgan_amd VisualLoss takes fp32 CUDA inputs")
+        if y_pred.dim() != 4 or y_pred.shape[1] != 3 or y_target.shape != y_pred.shape:
+            raise ValueError(f"VisualLoss: [B, 3, H, W] inputs of one shape are required, got {tuple(y_pred.shape)} "
+                             f"and {tuple(y_target.shape)}")
+        B, _, H, W = y_pred.shape
+        div = 1 << mod.num_pools
+        if H % div or W % div:
+            raise ValueError(f"VisualLoss: H={H} and W={W} must be divisible by {div} ({mod.num_pools} max-pools)")
+        dev = y_pred.device
+        packs, biases = mod.prepare(dev)
+        keep = ctx.needs_input_grad[1]
+        x = torch.empty((2 * B, H, W, 8), dtype=torch.bfloat16, device=dev)
+        ops.vgg_normalise(y_pred.detach(), x[:B])
+        ops.vgg_normalise(y_target.detach(), x[B:])
+        if tr is not None:
+            tr.update(input=x, items=[], acts=[], packed=packs, biases=biases)
+        saved, relu_in, li = [], False, 0
+        for it in mod.items:
+            if it[0] == "pool":
+                y = ops.maxpool2(x)
+                saved.append(("pool", x[:B], None))
+            else:
+                wf = packs[li][0]
+                y = torch.empty((2 * B, x.shape[1], x.shape[2], wf.shape[0]), dtype=torch.bfloat16, device=dev)
+                ops.conv3(x, wf, y, bias=biases[li], relu=True)
+                saved.append(("conv", x[:B], li, relu_in))
+                relu_in = True
+                li += 1
+            if tr is not None:
+                tr["items"].append(("conv", li - 1) if it[0] == "conv" else ("pool",))
+                tr["acts"].append(y)
+            x = y
+        fp, ft = x[:B], x[B:]
+        loss = ops.feature_mse(fp, ft)
+        if tr is not None:
+            tr["loss"] = loss
+        if keep:
+            ctx.mod, ctx.saved, ctx.feat, ctx.feat_relu = mod, saved, (fp, ft), relu_in
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        from . import ops
+        tr = TRACE if isinstance(TRACE, dict) else None
+        packs, _ = ctx.mod.prepare(gout.device)
+        fp, ft = ctx.feat
+        g = ops.feature_mse_backward(fp, ft, gout.contiguous().float(), relu_mask=ctx.feat_relu)
+        grads = []
+        if tr is not None:
+            tr["g_feat"] = g
+        for rec in reversed(ctx.saved):
+            xin = rec[1]
+            if rec[0] == "pool":
+                g = ops.maxpool2_backward(xin, g)
+            else:
+                gin = torch.empty_like(xin)
+                ops.conv3(g, packs[rec[2]][1], gin, bias=None, relu=False, mask=xin if rec[3] else None)
+                g = gin
+            grads.append(g)
+        dx = ops.vgg_normalise_backward(g)
+        if tr is not None:
+            tr["grads"] = grads[::-1]
+            tr["g_input"] = dx
+        return None, dx, None
+
+
+class VisualLoss(nn.Module):
+    """Perceptual loss of the reference's ``src/`` line (src/loss.py:29-56): F.mse_loss between the features of an
+    eval-mode, frozen ``vgg19_bn().features[:40]`` of the two images, each first mapped from the tanh range to the
+    ImageNet-normalised one.  ``features``: an nn.Sequential in torchvision's layout (``vgg19_bn_features``) made of
+    Conv2d(k=3, s=1, p=1) [+ BatchNorm2d] + ReLU groups and MaxPool2d(2, 2).  BatchNorm is folded into the conv at
+    construction (``refresh()`` folds again after loading weights); the chain runs in bf16 on the HIP 3x3 MFMA
+    kernels with fp32 accumulation.  Only ``y_pred`` receives a gradient.  The module holds no parameter and no
+    state_dict entry, and stays in eval mode whatever ``.train()`` is called on it."""
+
+    def __init__(self, features, norm=None, reduction: str = 'mean'):
+        super().__init__()
+        if reduction != 'mean' or (norm is not None and norm is not torch.nn.functional.mse_loss):
+            raise NotImplementedError("stcgan_amd VisualLoss: only F.mse_loss with reduction='mean' is on the path")
+        items = _parse_features(features)
+        features.requires_grad_(False).eval()
+        # (not a registered submodule: no parameter, no state_dict entry, nothing for .to() / the checkpoints)
+        self.__dict__["features"] = features
+        self.__dict__["items"] = items
+        self.reduction = reduction
+        self.num_pools = sum(1 for it in items if it[0] == "pool")
+        self.refresh()
+        super().train(False)
+
+    def train(self, mode: bool = True):
+        return super().train(False)
+
+    def refresh(self):
+        """Fold the BatchNorms into the convs again (after weights were loaded into ``features``), in fp32:
+        s = gamma / sqrt(running_var + eps), w' = w * s, b' = (b - running_mean) * s + beta (b = 0 without a bias)."""
+        folded = []
+        with torch.no_grad():
+            for it in self.items:
+                if it[0] != "conv":
+                    continue
+                conv, bn = it[1], it[2]
+                w = conv.weight.detach().float().cpu()
+                b = conv.bias.detach().float().cpu() if conv.bias is not None else torch.zeros(w.shape[0])
+                if bn is not None:
+                    gamma = bn.weight.detach().float().cpu() if bn.weight is not None else torch.ones(w.shape[0])
+                    beta = bn.bias.detach().float().cpu() if bn.bias is not None else torch.zeros(w.shape[0])
+                    s = gamma / torch.sqrt(bn.running_var.detach().float().cpu() + bn.eps)
+                    w = w * s[:, None, None, None]
+                    b = (b - bn.running_mean.detach().float().cpu()) * s + beta
+                folded.append((w.contiguous(), b.contiguous()))
+        self.__dict__["_folded"] = folded
+        self.__dict__["_packs"] = {}
+
+    def folded(self):
+        """Per conv layer (w' fp32 [Co, Ci, 3, 3], b' fp32 [Co])."""
+        return list(self._folded)
+
+    def prepare(self, device):
+        """The packed bf16 operands and fp32 biases on ``device`` (packed once per device and refresh())."""
+        from . import ops
+        key = str(device)
+        hit = self._packs.get(key)
+        if hit is None:
+            ws = [w.to(device) for w, _ in self._folded]
+            hit = self._packs[key] = (ops.pack_conv3(ws), [b.to(device) for _, b in self._folded])
+        return hit
+
+    def forward(self, y_pred, y_target):
+        return _VisualFn.apply(self, y_pred, y_target)

@@ -902,3 +902,109 @@ def grad_accumulate(pairs):
         src = (ctypes.c_void_p * n)(*[s.data_ptr() for _, s in chunk])
         num = (ctypes.c_int64 * n)(*[d.numel() for d, _ in chunk])
         check(lib().stc_grad_accumulate(n, dst, src, num, stream()), "stc_grad_accumulate")
+
+
+# ---- VisualLoss: vgg19_bn features in bf16 (stc_conv3_* / stc_maxpool2_* / stc_vgg_norm_* / stc_feat_mse_*) ----
+def _view(t):
+    """An NHWC bf16 tensor [B, H, W, C] or a ready View."""
+    return t if isinstance(t, L.View) else L.nhwc_view(t)
+
+
+def conv3_plan(B, H, W, cin, cout):
+    """stc_conv3_plan: (path, TH, TW, BN, K chunk, K splits, M tiles, N tiles)."""
+    key = ("c3plan", B, H, W, cin, cout)
+    v = _MEMO.get(key)
+    if v is None:
+        out = (ctypes.c_int32 * 8)()
+        check(lib().stc_conv3_plan(B, H, W, cin, cout, out), "stc_conv3_plan")
+        v = _MEMO[key] = tuple(out)
+    return v
+
+
+def pack_conv3(weights, want_dgrad=True):
+    """fp32 [Co, Ci, 3, 3] weights -> [(fwd bf16 [Co_pad, 9, Ci_pad], dgrad bf16 [Ci_pad, 9, Co_pad] or None)], channel
+    counts padded to multiples of 8; one stc_conv3_pack launch per 16 layers."""
+    out = []
+    for k in range(0, len(weights), L.CONV3_PACK_MAX):
+        chunk = [w.detach().float().contiguous() for w in weights[k:k + L.CONV3_PACK_MAX]]
+        descs = (L.Conv3PackDesc * len(chunk))()
+        for d, w in zip(descs, chunk):
+            if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not w.is_cuda:
+                raise ValueError(f"pack_conv3: a CUDA [Co, Ci, 3, 3] weight is required, got {tuple(w.shape)}")
+            co, ci = w.shape[:2]
+            cop, cip = -(-co // 8) * 8, -(-ci // 8) * 8
+            f = torch.empty((cop, 9, cip), dtype=torch.bfloat16, device=w.device)
+            g = torch.empty((cip, 9, cop), dtype=torch.bfloat16, device=w.device) if want_dgrad else None
+            d.W, d.fwd, d.dgrad = w.data_ptr(), f.data_ptr(), g.data_ptr() if g is not None else None
+            d.Co, d.Ci, d.Co_pad, d.Ci_pad = co, ci, cop, cip
+            out.append((f, g))
+        check(lib().stc_conv3_pack(len(chunk), descs, stream()), "stc_conv3_pack")
+    return out
+
+
+def conv3(x, w_packed, y, bias=None, relu=True, mask=None, B=None):
+    """stc_conv3_fwd: y = act(conv3x3(x, w_packed) + bias) [* (mask > 0)]; x, y, mask: NHWC bf16 tensors or Views
+    (then with B); w_packed: bf16 [Cout, 9, Cin]."""
+    xv, yv = _view(x), _view(y)
+    if B is None:
+        B = x.shape[0]
+    cout, _, cin = w_packed.shape
+    check(lib().stc_conv3_fwd(B, xv, cin, ptr(w_packed), cout, yv, ptr(bias), 1 if relu else 0,
+                              _view(mask) if mask is not None else L.NULL_VIEW, stream()), "stc_conv3_fwd")
+    return y
+
+
+def maxpool2(x, y=None):
+    """MaxPool2d(2, 2) of an NHWC bf16 tensor."""
+    B, H, W, C = x.shape
+    if y is None:
+        y = torch.empty((B, H // 2, W // 2, C), dtype=x.dtype, device=x.device)
+    check(lib().stc_maxpool2_fwd(B, L.nhwc_view(x), C, L.nhwc_view(y), stream()), "stc_maxpool2_fwd")
+    return y
+
+
+def maxpool2_backward(x, gy, gx=None):
+    """The gradient of maxpool2 at its input x (first maximal element of a window, torch's rule)."""
+    B, H, W, C = x.shape
+    if gx is None:
+        gx = torch.empty_like(x)
+    check(lib().stc_maxpool2_bwd(B, L.nhwc_view(x), C, L.nhwc_view(gy), L.nhwc_view(gx), stream()), "stc_maxpool2_bwd")
+    return gx
+
+
+def vgg_normalise(src, dst):
+    """((src * 0.5 + 0.5) - mean) / std of an fp32 [B, 3, H, W] tensor of any strides into the NHWC bf16 [B, H, W, 8]
+    tensor dst (channels 3..7 zero)."""
+    B, C, H, W = src.shape
+    if C != 3 or src.dtype != torch.float32:
+        raise ValueError(f"vgg_normalise: an fp32 [B, 3, H, W] tensor is required, got {tuple(src.shape)} {src.dtype}")
+    sb, sc, sh, sw = src.stride()
+    check(lib().stc_vgg_norm_fwd(B, H, W, ptr(src), sb, sc, sh, sw, L.nhwc_view(dst), stream()), "stc_vgg_norm_fwd")
+    return dst
+
+
+def vgg_normalise_backward(g):
+    """NHWC bf16 [B, H, W, 8] gradient of the normalised input -> contiguous fp32 [B, 3, H, W], times 0.5 / std."""
+    B, H, W, _ = g.shape
+    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=g.device)
+    check(lib().stc_vgg_norm_bwd(B, H, W, L.nhwc_view(g), ptr(out), stream()), "stc_vgg_norm_bwd")
+    return out
+
+
+def feature_mse(fp, ft):
+    """mean((fp - ft)^2) of two dense bf16 tensors as a 0-dim fp32 tensor (deterministic two-level sum)."""
+    assert fp.is_contiguous() and ft.is_contiguous() and fp.shape == ft.shape and fp.dtype == torch.bfloat16
+    n = fp.numel()
+    part = torch.empty(max(1, lib().stc_feat_mse_parts(n)), dtype=torch.float32, device=fp.device)
+    out = torch.empty((), dtype=torch.float32, device=fp.device)
+    check(lib().stc_feat_mse_fwd(ptr(fp), ptr(ft), n, ptr(part), ptr(out), stream()), "stc_feat_mse_fwd")
+    return out
+
+
+def feature_mse_backward(fp, ft, gout, relu_mask=False):
+    """bf16(gout * 2 (fp - ft) / n) [* (fp > 0)]; gout: fp32 device scalar."""
+    assert fp.is_contiguous() and ft.is_contiguous() and fp.shape == ft.shape and fp.dtype == torch.bfloat16
+    g = torch.empty_like(fp)
+    check(lib().stc_feat_mse_bwd(ptr(fp), ptr(ft), fp.numel(), ptr(gout), 1 if relu_mask else 0, ptr(g), stream()),
+          "stc_feat_mse_bwd")
+    return g

@@ -32,7 +32,8 @@ from . import engine
 from . import ops
 from . import networks
 from . import parallel
-from .loss import AdversarialLoss, DataLoss, d_objective, d_term_grad, g_objective
+from .loss import (AdversarialLoss, DataLoss, VisualLoss, d_objective, d_term_grad, g_objective,
+                   vgg19_bn_features)
 from .optim import Adam, AdamW
 
 
@@ -82,6 +83,34 @@ def accumulate(acc, vals, d_out, weight=1.0):
         acc[k] = acc[k] + v.double() * weight
     for k, c in zip(("D1_real", "D1_fake", "D2_real", "D2_fake"), d_out):
         acc[k] = acc[k] + c.mean().double() * weight
+
+
+def visual_loss_config(args):
+    """(lambda4, lambda5, VisualLoss or None) of the perceptual terms of the reference's ``src/`` line
+    (src/cgan.py:332-348): G_loss += lambda4 * vis1 + lambda5 * vis2 with vis1 = VisualLoss(m_pred expanded to 3
+    channels, m expanded), vis2 = VisualLoss(y_pred, y).  ``args.lambda4`` / ``args.lambda5`` default to 0: no
+    VisualLoss is built and nothing is launched.  The weights of a positive term come from ``args.visual_loss`` (a
+    ready loss.VisualLoss; takes precedence) or ``args.vgg_weights`` (the path of a torchvision ``vgg19_bn``
+    state_dict for torch.load); nothing is ever downloaded.  Needs no GPU."""
+    lam = []
+    for name in ("lambda4", "lambda5"):
+        v = float(getattr(args, name, 0.0))
+        if not v >= 0.0:
+            raise ValueError(f"stcgan_amd: args.{name} must be >= 0, got {v!r}")
+        lam.append(v)
+    if lam[0] == 0.0 and lam[1] == 0.0:
+        return 0.0, 0.0, None
+    vl = getattr(args, "visual_loss", None)
+    if vl is None:
+        path = getattr(args, "vgg_weights", None)
+        if path is None:
+            raise ValueError("stcgan_amd: args.lambda4 / args.lambda5 > 0 need the VGG-19-bn weights: set "
+                             "args.vgg_weights to the path of a torchvision vgg19_bn state_dict (torch.save'd), or "
+                             "args.visual_loss to a ready stcgan_amd.loss.VisualLoss")
+        vl = VisualLoss(vgg19_bn_features(torch.load(path, map_location="cpu", weights_only=True)))
+    elif not isinstance(vl, VisualLoss):
+        raise ValueError(f"stcgan_amd: args.visual_loss must be a stcgan_amd.loss.VisualLoss, got {type(vl).__name__}")
+    return lam[0], lam[1], vl
 
 
 def dropout_trainer_seeds(base, rank, world):
@@ -217,6 +246,11 @@ class STCGAN(object):
             self.lambda1 = 5     # data2 loss
             self.lambda2 = 0.1   # CGAN1 loss
             self.lambda3 = 0.1   # CGAN2 loss
+            # the perceptual terms of the src/ line (src/cgan.py:332-348), off by default (visual_loss_config); the
+            # VGG chain runs in bf16 whatever args.dtype is
+            self.lambda4, self.lambda5, self.visual_loss = visual_loss_config(args)
+            if self.visual_loss is not None:
+                self.visual_loss.prepare(self.device)  # packed operands made before any step (and any capture)
             self.adapt = getattr(args, "softadapt", False)
             self.weights_dir = getattr(args, "weights", None)
             self.log_interval = getattr(args, "log_every", 3)
@@ -509,6 +543,16 @@ class STCGAN(object):
                 data1_loss = self.data_loss(m_pred, m)
                 data2_loss = self.data_loss(y_pred, y)
                 G_loss = data1_loss + self.lambda1 * data2_loss + self.lambda2 * G1_loss + self.lambda3 * G2_loss
+            # the perceptual terms (src/cgan.py:332-348), torch scalar ops on top of the objective above, in this order:
+            # G = (G + lambda4 * vis1) + lambda5 * vis2; only an enabled term is computed
+            vis = {}
+            vl = getattr(self, "visual_loss", None)
+            if vl is not None and self.lambda4 > 0:
+                vis["vis1"] = vl(m_pred.expand(-1, 3, -1, -1), m.expand(-1, 3, -1, -1))
+                G_loss = G_loss + self.lambda4 * vis["vis1"]
+            if vl is not None and self.lambda5 > 0:
+                vis["vis2"] = vl(y_pred, y)
+                G_loss = G_loss + self.lambda5 * vis["vis2"]
             if training:
                 self._exchange(("G1", "G2"), 1)
                 weighted_loss(G_loss, weight).backward()
@@ -530,6 +574,8 @@ class STCGAN(object):
             engine.wait_stream(main, l2)
         vals = dict(D1=D1_loss.detach(), D2=D2_loss.detach(), D=D_loss.detach(), G1=G1_loss.detach(),
                     G2=G2_loss.detach(), data1=data1_loss.detach(), data2=data2_loss.detach(), G=G_loss.detach())
+        for k, v in vis.items():
+            vals[k] = v.detach()
         if acc is not None:
             accumulate(acc, vals, d_out, weight)
         return vals
@@ -605,6 +651,8 @@ class STCGAN(object):
             parallel.broadcast_buffers([self.G1, self.G2, self.D1, self.D2])
         self._lanes_stale = True  # (the broadcast above, a checkpoint load, a caller's writes between epochs)
         keys = ["G", "D", "D1", "D2", "G1", "G2", "data1", "data2"]
+        if getattr(self, "visual_loss", None) is not None:  # the enabled perceptual terms only
+            keys += [k for k, lam in (("vis1", self.lambda4), ("vis2", self.lambda5)) if lam > 0]
         # float64 sums, as the reference's Python-float accumulation of .item() values (STCGAN/stcgan.py:256-262,
         # 308-312) that ReduceLROnPlateau then reads
         acc = {k: torch.zeros((), dtype=torch.float64, device=self.device)

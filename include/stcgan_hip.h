@@ -353,7 +353,9 @@ int stc_dropout_next(int64_t* state, int64_t* call_state, void* stream);
 /* out[B][H][W][C] (uint8) = keep (1) / drop (0) over the full extent; C % 4 == 0 */
 int stc_dropout_mask(const stc_dropout* drop, int B, int C, uint8_t* out, void* stream);
 /* stc_bn_apply with the dropout between the affine and the activation(s): y = act(n * keep/(1-p), slope); x's extent
- * may be a crop (rows / columns from 0) of the full extent.  stc_conv_bn_fwd_drop: stc_conv_bn_fwd with this apply. */
+ * may be a crop (rows / columns from 0) of the full extent.  stc_conv_bn_fwd_drop: stc_conv_bn_fwd with this apply;
+ * a dropout block or activation views that the apply refuses are refused before the conv is launched (the raw
+ * output and the running statistics stay as they were). */
 int stc_bn_apply_drop(int dtype, int B, stc_view x, int C, const float* scale, const float* shift,
                       stc_view y1, float slope1, stc_view y2, float slope2, const stc_dropout* drop, void* stream);
 int stc_conv_bn_fwd_drop(int dtype, int kind, int B, stc_view x, int Cin, const void* w_packed, int Cout, stc_view y,

@@ -1212,6 +1212,13 @@ extern "C" int stc_conv_bn_fwd_drop(int dtype, int kind, int B, stc_view x, int 
   STC_REQUIRE(y1.p, "stc_conv_bn_fwd_drop: an apply output is required");
   DropDev dd;
   if (int rc = mkdrop(drop, B, Cout, &dd, "stc_conv_bn_fwd_drop")) return rc;  // (before anything is launched)
+  // what stc_bn_apply_drop would refuse, also before the conv and the finalize: a refused call leaves the raw
+  // output and the running statistics alone
+  STC_REQUIRE(vec_ok(dtype, Cout, apply_x) && vec_ok(dtype, Cout, y1) && (!y2.p || vec_ok(dtype, Cout, y2)),
+              "stc_conv_bn_fwd_drop: C=%d / activation views not 16-byte vectorisable NHWC", Cout);
+  STC_REQUIRE(apply_x.H <= drop->H && apply_x.W <= drop->W,
+              "stc_conv_bn_fwd_drop: view %d x %d outside the dropout extent %d x %d", apply_x.H, apply_x.W, drop->H,
+              drop->W);
   int rc = stc_conv_fwd_ex(dtype, kind, B, x, Cin, w_packed, Cout, y, nullptr, 0, 0, fws, nchunks, nullptr, workspace,
                            workspace_bytes, stream);
   if (rc) return rc;

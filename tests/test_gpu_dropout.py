@@ -63,6 +63,8 @@ class _Case:
         self.mean, self.rstd = ops.bn_train_table(B, self.xv, C, dt, self.bn, self.tab[0], self.tab[1])
         self.state = _state()
         self.mask = ops.dropout_mask(self.state, LEVEL, (B, FH, FW, C))  # p = 0.5
+        # (the reference of the tests below is built from this mask: it is the numpy restatement's, not only the GPU's)
+        assert np.array_equal(self.mask.cpu().numpy(), np_mask(SEED, OFFSET, LEVEL, (B, FH, FW, C), 0.5))
 
     def drop(self, p):
         return (self.state, LEVEL, p, FH, FW)

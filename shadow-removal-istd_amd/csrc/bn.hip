@@ -9,10 +9,20 @@
 // Backward: dn = g1*act1'(n) + g2*act2'(n) is recomputed on the fly from the raw
 // input (n = x*scale + shift), reduced to sum(dn), sum(dn*xhat), then applied.
 // All reductions are fixed-order => bitwise reproducible.
+//
+// Each piece is stated once and the kernels are thin users of it, but for the reduction layout, which
+// chan_stats_kernel still repeats (see there):
+//   ChunkReduce          the per-chunk reduction skeleton (chan_sum, bn_bwd_reduce)
+//   WaveMerge/BlockMerge the two reduction policies of the chunk merges (bn_finalize, bn_bwd_finalize)
+//   NoMask/PhiloxMask    the compile-time dropout policy (bn_bwd_reduce; the *_drop element-wise kernels)
+//   bn_fwd_emit          the forward per element: n, the optional mask, one or two activations
+//   bn_bwd_table/_dx     the backward per element: the k0/k1/k2 table and dx from (v, g1, g2, mask); dn_term is
+//                        one gradient's term of dn (dn_add: of a whole vector, as the reduce adds it)
 #include <type_traits>
 
 #include "common.hpp"
 #include "philox.hpp"
+#include "vec16.hpp"
 
 namespace stc {
 
@@ -24,36 +34,6 @@ __host__ __device__ inline int stat_chunks(long long P) {
   if (c < 1) c = 1;
   return (int)c;
 }
-
-// ---- 16-byte vectors of T (8 bf16 / 4 fp32 channels per thread)
-template <typename T> struct VW;
-template <> struct VW<float> {
-  static constexpr int N = 4;
-  __device__ __forceinline__ static void load(const float* p, float* f) {
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-  }
-  __device__ __forceinline__ static void store(float* p, const float* f) {
-    *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-  }
-};
-template <> struct VW<bf16> {
-  static constexpr int N = 8;
-  __device__ __forceinline__ static void load(const bf16* p, float* f) {
-    const uint4 v = *reinterpret_cast<const uint4*>(p);
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { f[2 * q] = __uint_as_float(w[q] << 16); f[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u); }
-  }
-  __device__ __forceinline__ static void store(bf16* p, const float* f) {
-    uint4 v;
-    v.x = (unsigned)f2bf(f[0]) | ((unsigned)f2bf(f[1]) << 16);
-    v.y = (unsigned)f2bf(f[2]) | ((unsigned)f2bf(f[3]) << 16);
-    v.z = (unsigned)f2bf(f[4]) | ((unsigned)f2bf(f[5]) << 16);
-    v.w = (unsigned)f2bf(f[6]) | ((unsigned)f2bf(f[7]) << 16);
-    *reinterpret_cast<uint4*>(p) = v;
-  }
-};
 
 // pixel index -> (b, y, x); exact float-reciprocal division below 2^24 pixels, integer division above
 struct PixDiv {
@@ -68,11 +48,6 @@ static inline PixDiv mkpix(int B, int H, int W) {
   d.big = (long long)B * H * W >= (1ll << 24);
   return d;
 }
-__device__ __forceinline__ int qdiv(int n, int d, float inv) {
-  int q = (int)((float)n * inv);
-  const int r = n - q * d;
-  return q + (r >= d) - (r < 0);
-}
 __device__ __forceinline__ void pix_bxy(const PixDiv& d, long long pix, int& b, int& y, int& x) {
   int rem;
   if (d.big) {
@@ -81,9 +56,9 @@ __device__ __forceinline__ void pix_bxy(const PixDiv& d, long long pix, int& b, 
     y = rem / d.W;
   } else {
     const int pi = (int)pix;
-    b = qdiv(pi, d.HW, d.inv_hw);
+    b = fast_div(pi, d.HW, d.inv_hw);
     rem = pi - b * d.HW;
-    y = qdiv(rem, d.W, d.inv_w);
+    y = fast_div(rem, d.W, d.inv_w);
   }
   x = rem - y * d.W;
 }
@@ -93,12 +68,84 @@ __device__ __forceinline__ const T* vptr(const View& v, int b, int y, int x, int
   return reinterpret_cast<const T*>(v.p) + vidx(v, b, y, x, c);
 }
 
-// Reduction layout shared by the per-channel reductions: thread = (channel group cg of N channels,
-// pixel lane pl); the block owns a contiguous pixel range and the lanes stride through it.
+// (scale, shift) of the N channels from c; the identity without a table
+template <int N>
+__device__ __forceinline__ void ld_affine(const float* scale, const float* shift, int c, float* sc, float* sh) {
+  if (scale) { ldc<N>(scale + c, sc); ldc<N>(shift + c, sh); }
+  else {
+#pragma unroll
+    for (int e = 0; e < N; ++e) { sc[e] = 1.f; sh[e] = 0.f; }
+  }
+}
+
+// ---- dropout policy of the kernels that exist with and without a mask (philox.hpp holds the mask function)
+struct NoMask {
+  static constexpr bool ON = false;
+  struct Key {};
+  __device__ __forceinline__ Key key() const { return Key{}; }
+};
+struct PhiloxMask {
+  static constexpr bool ON = true;
+  using Key = DropKey;
+  DropDev d;
+  __device__ __forceinline__ Key key() const { return drop_key(d); }
+  // logical index of the vector's first element
+  __device__ __forceinline__ unsigned long long index(int C, int b, int y, int x, int c) const {
+    return drop_index(d, C, b, y, x, c);
+  }
+  template <int N>
+  __device__ __forceinline__ void factor(const Key& k, unsigned long long li, float* m) const {
+    drop_factor<N>(d, k, li, m);
+  }
+};
+
+// Skeleton of the per-channel chunk reductions.  Thread = (channel group cg of N channels, pixel lane pl);
+// block blockIdx.x owns the contiguous pixel range [p0, p1) and its RL lanes stride through it, each adding
+// its pixels in order into its ROW accumulators; lane 0 of every channel group then adds the lanes' rows in
+// lane order (fixed order).
+template <int ROW>
+struct ChunkReduce {
+  int CG, RL, cg, pl;
+  long long p0, p1;
+  __device__ __forceinline__ ChunkReduce(long long P, int CG_, int nchunks)
+      : CG(CG_), RL(256 / CG_), cg(threadIdx.x % CG_), pl(threadIdx.x / CG_) {
+    const long long per = (P + nchunks - 1) / nchunks;
+    p0 = blockIdx.x * per;
+    p1 = min(P, p0 + per);
+  }
+  // init() once, then pixel(pix) for each of this lane's pixels; both add into the caller's acc[ROW].
+  // Returns true on the pl == 0 threads, whose acc then holds the chunk's totals.
+  template <class Init, class Pixel>
+  __device__ __forceinline__ bool run(float* acc, Init&& init, Pixel&& pixel) {
+    __shared__ float red[256][ROW];
+    if (pl < RL) {
+      init();
+#pragma unroll 4
+      for (long long pix = p0 + pl; pix < p1; pix += RL) pixel(pix);
+    }
+#pragma unroll
+    for (int j = 0; j < ROW; ++j) red[threadIdx.x][j] = acc[j];
+    __syncthreads();
+    if (pl != 0) return false;
+    float tot[ROW];  // (its own registers: summed into acc itself, the loop fills with register copies)
+#pragma unroll
+    for (int j = 0; j < ROW; ++j) tot[j] = 0.f;
+    for (int k = 0; k < RL; ++k) {  // fixed order
+      const int t = k * CG + cg;
+#pragma unroll
+      for (int j = 0; j < ROW; ++j) tot[j] += red[t][j];
+    }
+#pragma unroll
+    for (int j = 0; j < ROW; ++j) acc[j] = tot[j];
+    return true;
+  }
+};
+
+// (chan_stats_kernel keeps its own copy of the ChunkReduce layout: through the skeleton its bf16 form took 25 % longer)
 // part[chunk][c] = {n, S1, S2, shift}
 template <typename T>
 __global__ void __launch_bounds__(256) chan_stats_kernel(View x, PixDiv pd, long long P, int C, float* part, int nchunks) {
-  constexpr int N = VW<T>::N;
+  constexpr int N = Vec16<T>::N;
   const int CG = C / N;
   const int RL = 256 / CG;
   const int cg = threadIdx.x % CG, pl = threadIdx.x / CG;
@@ -111,12 +158,12 @@ __global__ void __launch_bounds__(256) chan_stats_kernel(View x, PixDiv pd, long
   if (pl < RL && p0 < p1) {
     int b, yy, xx;
     pix_bxy(pd, p0, b, yy, xx);
-    VW<T>::load(vptr<T>(x, b, yy, xx, N * cg), sh);
+    Vec16<T>::load(vptr<T>(x, b, yy, xx, N * cg), sh);
 #pragma unroll 4
     for (long long pix = p0 + pl; pix < p1; pix += RL) {
       pix_bxy(pd, pix, b, yy, xx);
       float v[N];
-      VW<T>::load(vptr<T>(x, b, yy, xx, N * cg), v);
+      Vec16<T>::load(vptr<T>(x, b, yy, xx, N * cg), v);
 #pragma unroll
       for (int e = 0; e < N; ++e) {
         const float d = v[e] - sh[e];
@@ -146,34 +193,51 @@ __global__ void __launch_bounds__(256) chan_stats_kernel(View x, PixDiv pd, long
   }
 }
 
+// ---- reduction policies of the chunk merges: which lanes share a channel, and their fp64 total
+// one wave per channel, 4 channels per block, no block barriers: a merge runs once per BatchNorm per pass, so
+// its latency, not its bytes, is what it costs
+struct WaveMerge {
+  static constexpr int LANES = 64, CPB = 4;
+  __device__ __forceinline__ static int lane() { return threadIdx.x & 63; }
+  __device__ __forceinline__ static int channel() { return blockIdx.x * 4 + (threadIdx.x >> 6); }
+  __device__ __forceinline__ static double sum(double v) { return wave_sum(v); }
+};
+// one block per channel (butterfly within each wave, then the 4 wave totals in a fixed order: deterministic, 2 barriers)
+struct BlockMerge {
+  static constexpr int LANES = 256, CPB = 1;
+  __device__ __forceinline__ static int lane() { return threadIdx.x; }
+  __device__ __forceinline__ static int channel() { return blockIdx.x; }
+  __device__ __forceinline__ static double sum(double v) {
+    __shared__ double sh[256];
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    __syncthreads();
+    return r;
+  }
+};
+template <class R> static dim3 merge_grid(int C) { return dim3((C + R::CPB - 1) / R::CPB); }
+
 // Merge of the per-chunk statistics {n, S1 = sum(x - shift), S2 = sum((x - shift)^2), shift}:
 // chunk mean m_b = shift + S1/n, chunk M2_b = S2 - S1^2/n; then (exactly, in fp64)
 //   mean = sum n_b m_b / N,   M2 = sum [M2_b + n_b (m_b - mean)^2]
-// in two passes over the chunks (one block per channel, fixed-order tree -> deterministic).
-// (butterfly within each wave, then the 4 wave totals in a fixed order: deterministic, 2 barriers)
-__device__ __forceinline__ double block_sum256(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return r;
-}
-
+// in two passes over the chunks (the policy's lanes per channel, fixed-order tree -> deterministic).
+template <class R>
 __global__ void __launch_bounds__(256) bn_finalize_kernel(const float* part, int nchunks, int C,
                                                           const float* gamma, const float* beta,
                                                           float* rmean, float* rvar, long long* nbt,
                                                           float momentum, float eps,
                                                           float* mean_o, float* rstd_o, float* scale, float* shift) {
-  const int c = blockIdx.x;
-  __shared__ double sh[256];
-  // chunk partials are read in groups of 4 per thread (the 4 loads in flight together: one
+  constexpr int L = R::LANES;
+  const int lane = R::lane(), c = R::channel();
+  if (R::CPB > 1 && c >= C) return;
+  // chunk partials are read in groups of 4 per lane (the 4 loads in flight together: one
   // memory latency per group -- the first layers merge up to 4096 chunks per channel)
   auto load4 = [&](int k0, float4* pp) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const int k = k0 + u * 256;
+      const int k = k0 + u * L;
       pp[u] = k < nchunks ? *reinterpret_cast<const float4*>(part + ((long long)k * C + c) * 4)
                           : make_float4(0.f, 0.f, 0.f, 0.f);
     }
@@ -198,134 +262,45 @@ __global__ void __launch_bounds__(256) bn_finalize_kernel(const float* part, int
       m2 += q + nb * d * d;
     }
   };
-  // up to 4096 chunks: every thread loads its (up to) 4 groups of 4 partials at once and keeps them in registers
+  // up to 16 L chunks: every lane loads its (up to) 4 groups of 4 partials at once and keeps them in registers
   // for both passes (one memory latency); the sums run in the loop's order below, so the results are the same
   auto in_regs = [&](auto Gc, double& n, double& sm, double& m2) {
     constexpr int G = decltype(Gc)::value;
     float4 pp[G][4];
 #pragma unroll
-    for (int g = 0; g < G; ++g) load4(threadIdx.x + 1024 * g, pp[g]);
+    for (int g = 0; g < G; ++g) load4(lane + 4 * L * g, pp[g]);
 #pragma unroll
     for (int g = 0; g < G; ++g) sum1(pp[g], n, sm);
-    n = block_sum256(n, sh);
-    sm = block_sum256(sm, sh);
-    const double mu = n > 0 ? sm / n : 0.0;
-#pragma unroll
-    for (int g = 0; g < G; ++g) sum2(pp[g], mu, m2);
-    sm = mu;
-  };
-  double n = 0, sm = 0, m2 = 0;
-  if (nchunks <= 1024) {
-    in_regs(std::integral_constant<int, 1>{}, n, sm, m2);
-  } else if (nchunks <= 2048) {
-    in_regs(std::integral_constant<int, 2>{}, n, sm, m2);
-  } else if (nchunks <= 4096) {
-    in_regs(std::integral_constant<int, 4>{}, n, sm, m2);
-  } else {
-    for (int k0 = threadIdx.x; k0 < nchunks; k0 += 1024) {
-      float4 pp[4];
-      load4(k0, pp);
-      sum1(pp, n, sm);
-    }
-    n = block_sum256(n, sh);
-    sm = block_sum256(sm, sh);
-    const double mu = n > 0 ? sm / n : 0.0;
-    for (int k0 = threadIdx.x; k0 < nchunks; k0 += 1024) {
-      float4 pp[4];
-      load4(k0, pp);
-      sum2(pp, mu, m2);
-    }
-    sm = mu;
-  }
-  const double N = n, mu = sm;
-  const double M2 = block_sum256(m2, sh);
-  if (threadIdx.x == 0)
-    bn_finalize_store(c, N, mu, M2, pre, rmean, rvar, nbt, momentum, eps, mean_o, rstd_o, scale, shift);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// The same merge with one wave per channel (4 channels per block, no block barriers): the
-// finalize runs once per BatchNorm per pass, so its latency, not its bytes, is what it costs.
-__global__ void __launch_bounds__(256) bn_finalize_wave_kernel(const float* part, int nchunks, int C,
-                                                               const float* gamma, const float* beta,
-                                                               float* rmean, float* rvar, long long* nbt,
-                                                               float momentum, float eps,
-                                                               float* mean_o, float* rstd_o, float* scale, float* shift) {
-  const int lane = threadIdx.x & 63;
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (c >= C) return;
-  auto load4 = [&](int k0, float4* pp) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int k = k0 + u * 64;
-      pp[u] = k < nchunks ? *reinterpret_cast<const float4*>(part + ((long long)k * C + c) * 4)
-                          : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  const BnPre pre = bn_pre(c, gamma, beta, rmean, rvar);  // (issued with the partials' loads)
-  auto sum1 = [&](const float4* pp, double& n, double& sm) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (pp[u].x <= 0.f) continue;
-      n += pp[u].x;
-      sm += (double)pp[u].x * pp[u].w + (double)pp[u].y;
-    }
-  };
-  auto sum2 = [&](const float4* pp, double mu, double& m2) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (pp[u].x <= 0.f) continue;
-      const double nb = pp[u].x, s1 = pp[u].y, r = s1 / nb;
-      double q = (double)pp[u].z - s1 * r;
-      if (q < 0) q = 0;
-      const double d = (double)pp[u].w + r - mu;
-      m2 += q + nb * d * d;
-    }
-  };
-  // up to 1024 chunks: every lane loads its (up to) 4 groups of 4 partials at once and keeps them in registers for
-  // both passes (one memory latency); the sums run in the loop's order below, so the results are the same
-  auto in_regs = [&](auto Gc, double& n, double& sm, double& m2) {
-    constexpr int G = decltype(Gc)::value;
-    float4 pp[G][4];
-#pragma unroll
-    for (int g = 0; g < G; ++g) load4(lane + 256 * g, pp[g]);
-#pragma unroll
-    for (int g = 0; g < G; ++g) sum1(pp[g], n, sm);
-    n = wave_sum(n);
-    sm = wave_sum(sm);
+    n = R::sum(n);
+    sm = R::sum(sm);
     const double mu = n > 0 ? sm / n : 0.0;
 #pragma unroll
     for (int g = 0; g < G; ++g) sum2(pp[g], mu, m2);
     return mu;
   };
   double n = 0, sm = 0, m2 = 0, mu;
-  if (nchunks <= 256) {
+  if (nchunks <= 4 * L) {
     mu = in_regs(std::integral_constant<int, 1>{}, n, sm, m2);
-  } else if (nchunks <= 512) {
+  } else if (nchunks <= 8 * L) {
     mu = in_regs(std::integral_constant<int, 2>{}, n, sm, m2);
-  } else if (nchunks <= 1024) {
+  } else if (nchunks <= 16 * L) {
     mu = in_regs(std::integral_constant<int, 4>{}, n, sm, m2);
   } else {
-    for (int k0 = lane; k0 < nchunks; k0 += 256) {
+    for (int k0 = lane; k0 < nchunks; k0 += 4 * L) {
       float4 pp[4];
       load4(k0, pp);
       sum1(pp, n, sm);
     }
-    n = wave_sum(n);
-    sm = wave_sum(sm);
+    n = R::sum(n);
+    sm = R::sum(sm);
     mu = n > 0 ? sm / n : 0.0;
-    for (int k0 = lane; k0 < nchunks; k0 += 256) {
+    for (int k0 = lane; k0 < nchunks; k0 += 4 * L) {
       float4 pp[4];
       load4(k0, pp);
       sum2(pp, mu, m2);
     }
   }
-  const double M2 = wave_sum(m2);
+  const double M2 = R::sum(m2);
   if (lane == 0) bn_finalize_store(c, n, mu, M2, pre, rmean, rvar, nbt, momentum, eps, mean_o, rstd_o, scale, shift);
 }
 
@@ -346,98 +321,125 @@ struct GradIn {
   int has1, has2;
 };
 
-template <typename T>
-__device__ __forceinline__ void dn_of(const GradIn& gi, int b, int y, int x, int c, const float* n, float* d) {
-  constexpr int N = VW<T>::N;
+// One gradient's term of dn = g1*act1'(n) + g2*act2'(n); MASKED: g reaches n through the dropout, g * keep/(1-p)
+template <bool MASKED>
+__device__ __forceinline__ float dn_term(float g, float m, float n, float slope) {
+  if constexpr (MASKED) return (g * m) * dact(n, slope);
+  else return g * dact(n, slope);
+}
+// ... of a whole vector (the reduce adds a gradient's term right after that gradient's load)
+template <int N, bool MASKED>
+__device__ __forceinline__ void dn_add(const float* g, const float* m, const float* n, float slope, float* dn) {
 #pragma unroll
-  for (int e = 0; e < N; ++e) d[e] = 0.f;
-  if (gi.has1) {
-    float g[N];
-    VW<T>::load(vptr<T>(gi.g1, b, y, x, c), g);
+  for (int e = 0; e < N; ++e) dn[e] += dn_term<MASKED>(g[e], MASKED ? m[e] : 1.f, n[e], slope);
+}
+
+// The backward per element, for the N channels from c:
+// n = v*sc + sh;  dx = k1*dn - k0 - k2*v   with k1 = gamma*rstd, k2 = k1*rstd*dgamma/P,
+// k0 = k1*(dbeta/P - mean*rstd*dgamma/P); without mean (activation only) dx = dn.
+// MASKED: g1 is required and carries the dropout factor m.
+// CHECKED = false: the entry point has required every table (the _drop calls), so the tests for an absent scale or
+// mean are compiled out -- behind them the compiler contracts k0's products differently and dx's last bit moves.
+template <int N, bool CHECKED = true>
+__device__ __forceinline__ void bn_bwd_table(int c, const float* scale, const float* shift, const float* mean,
+                                             const float* rstd, const float* gamma, const float* dgamma,
+                                             const float* dbeta, float invP, float* sc, float* sh, float* k0,
+                                             float* k1, float* k2) {
+  if (CHECKED) ld_affine<N>(scale, shift, c, sc, sh);
+  else { ldc<N>(scale + c, sc); ldc<N>(shift + c, sh); }
+  if (!CHECKED || mean) {
+    float mu[N], rs[N], gm[N], dg[N], db[N];
+    ldc<N>(mean + c, mu); ldc<N>(rstd + c, rs); ldc<N>(gamma + c, gm); ldc<N>(dgamma + c, dg); ldc<N>(dbeta + c, db);
 #pragma unroll
-    for (int e = 0; e < N; ++e) d[e] += g[e] * dact(n[e], gi.s1);
+    for (int e = 0; e < N; ++e) {
+      k1[e] = gm[e] * rs[e];
+      k2[e] = k1[e] * rs[e] * dg[e] * invP;
+      k0[e] = k1[e] * (db[e] * invP - mu[e] * rs[e] * dg[e] * invP);
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < N; ++e) { k1[e] = 1.f; k2[e] = 0.f; k0[e] = 0.f; }
   }
-  if (gi.has2) {
-    float g[N];
-    VW<T>::load(vptr<T>(gi.g2, b, y, x, c), g);
+}
+template <int N, bool MASKED>
+__device__ __forceinline__ void bn_bwd_dx(const GradIn& gi, const float* sc, const float* sh, const float* k0,
+                                          const float* k1, const float* k2, const float* v, const float* g1,
+                                          const float* g2, const float* m, float* d) {
 #pragma unroll
-    for (int e = 0; e < N; ++e) d[e] += g[e] * dact(n[e], gi.s2);
+  for (int e = 0; e < N; ++e) {
+    const float n = fmaf(v[e], sc[e], sh[e]);
+    float dn = 0.f;
+    if constexpr (MASKED) dn += dn_term<true>(g1[e], m[e], n, gi.s1);
+    else if (gi.has1) dn += dn_term<false>(g1[e], 1.f, n, gi.s1);
+    if (gi.has2) dn += dn_term<false>(g2[e], 1.f, n, gi.s2);
+    d[e] = fmaf(k1[e], dn, -fmaf(k2[e], v[e], k0[e]));
   }
 }
 
-template <int N>
-__device__ __forceinline__ void ldc(const float* p, float* f) {
-#pragma unroll
-  for (int e = 0; e < N; e += 4) {
-    const float4 v = *reinterpret_cast<const float4*>(p + e);
-    f[e] = v.x; f[e + 1] = v.y; f[e + 2] = v.z; f[e + 3] = v.w;
-  }
-}
-
-// part2[chunk][c] = {sum dn, sum dn*xhat}
-template <typename T>
+// part2[chunk][c] = {sum dn, sum dn*xhat}.  With PhiloxMask g1 is required and no mask is stored: it is
+// recomputed from the call's counter.
+template <typename T, class M>
 __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(View x, PixDiv pd, long long P, int C, const float* scale,
                                                             const float* shift, const float* mean, const float* rstd,
-                                                            GradIn gi, float* part, int nchunks) {
-  constexpr int N = VW<T>::N;
-  const int CG = C / N;
-  const int RL = 256 / CG;
-  const int cg = threadIdx.x % CG, pl = threadIdx.x / CG;
-  const long long per = (P + nchunks - 1) / nchunks;
-  const long long p0 = blockIdx.x * per, p1 = min(P, p0 + per);
-  __shared__ float red[256][2 * N];
-  float a[N], bs[N];
+                                                            GradIn gi, float* part, int nchunks, M mask) {
+  constexpr int N = Vec16<T>::N;
+  ChunkReduce<2 * N> r(P, C / N, nchunks);
+  const int c = N * r.cg;
+  float acc[2 * N], sc[N], shf[N], mu[N], rs[N];  // acc = {sum dn [N], sum dn*xhat [N]}
+  typename M::Key key;
 #pragma unroll
-  for (int e = 0; e < N; ++e) { a[e] = 0.f; bs[e] = 0.f; }
-  if (pl < RL) {
-    const int c = N * cg;
-    float sc[N], shf[N], mu[N], rs[N];
-    ldc<N>(scale + c, sc); ldc<N>(shift + c, shf); ldc<N>(mean + c, mu); ldc<N>(rstd + c, rs);
-#pragma unroll 4
-    for (long long pix = p0 + pl; pix < p1; pix += RL) {
-      int b, yy, xx;
-      pix_bxy(pd, pix, b, yy, xx);
-      float v[N], n[N], d[N];
-      VW<T>::load(vptr<T>(x, b, yy, xx, c), v);
+  for (int j = 0; j < 2 * N; ++j) acc[j] = 0.f;
+  const bool lead = r.run(
+      acc,
+      [&] {
+        key = mask.key();
+        ldc<N>(scale + c, sc); ldc<N>(shift + c, shf); ldc<N>(mean + c, mu); ldc<N>(rstd + c, rs);
+      },
+      // (4 pixels' loads and Philox rounds in flight together; the sums stay in pixel order)
+      [&](long long pix) {
+        int b, yy, xx;
+        pix_bxy(pd, pix, b, yy, xx);
+        float v[N], n[N], d[N];
+        Vec16<T>::load(vptr<T>(x, b, yy, xx, c), v);
 #pragma unroll
-      for (int e = 0; e < N; ++e) n[e] = fmaf(v[e], sc[e], shf[e]);
-      dn_of<T>(gi, b, yy, xx, c, n, d);
+        for (int e = 0; e < N; ++e) { n[e] = fmaf(v[e], sc[e], shf[e]); d[e] = 0.f; }
+        if (M::ON || gi.has1) {
+          float g[N], m[N];
+          Vec16<T>::load(vptr<T>(gi.g1, b, yy, xx, c), g);
+          if constexpr (M::ON) mask.template factor<N>(key, mask.index(C, b, yy, xx, c), m);
+          dn_add<N, M::ON>(g, m, n, gi.s1, d);
+        }
+        if (gi.has2) {
+          float g[N];
+          Vec16<T>::load(vptr<T>(gi.g2, b, yy, xx, c), g);
+          dn_add<N, false>(g, nullptr, n, gi.s2, d);
+        }
 #pragma unroll
-      for (int e = 0; e < N; ++e) {
-        a[e] += d[e];
-        bs[e] += d[e] * (v[e] - mu[e]) * rs[e];
-      }
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < N; ++e) { red[threadIdx.x][e] = a[e]; red[threadIdx.x][N + e] = bs[e]; }
-  __syncthreads();
-  if (pl == 0) {
-    float r0[N], r1[N];
-#pragma unroll
-    for (int e = 0; e < N; ++e) { r0[e] = 0.f; r1[e] = 0.f; }
-    for (int k = 0; k < RL; ++k) {
-      const int t = k * CG + cg;
-#pragma unroll
-      for (int e = 0; e < N; ++e) { r0[e] += red[t][e]; r1[e] += red[t][N + e]; }
-    }
+        for (int e = 0; e < N; ++e) {
+          acc[e] += d[e];
+          acc[N + e] += d[e] * (v[e] - mu[e]) * rs[e];
+        }
+      });
+  if (lead) {
 #pragma unroll
     for (int e = 0; e < N; ++e)
-      *reinterpret_cast<float2*>(part + ((long long)blockIdx.x * C + N * cg + e) * 2) = make_float2(r0[e], r1[e]);
+      *reinterpret_cast<float2*>(part + ((long long)blockIdx.x * C + c + e) * 2) = make_float2(acc[e], acc[N + e]);
   }
 }
 
-// dbeta[c] = sum dn, dgamma[c] = sum dn*xhat  (fixed order over chunks, one block per channel)
+// dbeta[c] = sum dn, dgamma[c] = sum dn*xhat  (fixed order over chunks, the policy's lanes per channel)
+template <class R>
 __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(const float* part, int nchunks, int C, float* dgamma,
                                                               float* dbeta) {
-  const int c = blockIdx.x;
-  __shared__ double sh[256];
+  constexpr int L = R::LANES;
+  const int lane = R::lane(), c = R::channel();
+  if (R::CPB > 1 && c >= C) return;
   double a = 0, b = 0;
-  for (int k0 = threadIdx.x; k0 < nchunks; k0 += 1024) {  // groups of 4 loads in flight
+  for (int k0 = lane; k0 < nchunks; k0 += 4 * L) {  // groups of 4 loads in flight
     float2 pp[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const int k = k0 + u * 256;
+      const int k = k0 + u * L;
       pp[u] = k < nchunks ? *reinterpret_cast<const float2*>(part + ((long long)k * C + c) * 2) : make_float2(0.f, 0.f);
     }
 #pragma unroll
@@ -446,36 +448,8 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(const float* part,
       b += pp[u].y;
     }
   }
-  const double ta = block_sum256(a, sh);
-  const double tb = block_sum256(b, sh);
-  if (threadIdx.x == 0) {
-    dbeta[c] = (float)ta;
-    dgamma[c] = (float)tb;
-  }
-}
-
-// one wave per channel (4 per block): as bn_bwd_finalize_kernel without block barriers
-__global__ void __launch_bounds__(256) bn_bwd_finalize_wave_kernel(const float* part, int nchunks, int C, float* dgamma,
-                                                                   float* dbeta) {
-  const int lane = threadIdx.x & 63;
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (c >= C) return;
-  double a = 0, b = 0;
-  for (int k0 = lane; k0 < nchunks; k0 += 256) {
-    float2 pp[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int k = k0 + u * 64;
-      pp[u] = k < nchunks ? *reinterpret_cast<const float2*>(part + ((long long)k * C + c) * 2) : make_float2(0.f, 0.f);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      a += pp[u].x;
-      b += pp[u].y;
-    }
-  }
-  a = wave_sum(a);
-  b = wave_sum(b);
+  a = R::sum(a);
+  b = R::sum(b);
   if (lane == 0) {
     dbeta[c] = (float)a;
     dgamma[c] = (float)b;
@@ -487,7 +461,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(View x, PixDiv pd, lo
                                                            const float* shift, const float* mean, const float* rstd,
                                                            const float* gamma, GradIn gi, const float* dgamma,
                                                            const float* dbeta, View dx) {
-  constexpr int N = VW<T>::N;
+  constexpr int N = Vec16<T>::N;
   const int CG = C / N;
   const long long total = P * CG;
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -501,25 +475,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(View x, PixDiv pd, lo
   auto table = [&](int cg) {
     if (cg == cg_have) return;
     cg_have = cg;
-    const int c = N * cg;
-    if (scale) { ldc<N>(scale + c, sc); ldc<N>(shift + c, sh); }
-    else {
-#pragma unroll
-      for (int e = 0; e < N; ++e) { sc[e] = 1.f; sh[e] = 0.f; }
-    }
-    if (mean) {
-      float mu[N], rs[N], gm[N], dg[N], db[N];
-      ldc<N>(mean + c, mu); ldc<N>(rstd + c, rs); ldc<N>(gamma + c, gm); ldc<N>(dgamma + c, dg); ldc<N>(dbeta + c, db);
-#pragma unroll
-      for (int e = 0; e < N; ++e) {
-        k1[e] = gm[e] * rs[e];
-        k2[e] = k1[e] * rs[e] * dg[e] * invP;
-        k0[e] = k1[e] * (db[e] * invP - mu[e] * rs[e] * dg[e] * invP);
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < N; ++e) { k1[e] = 1.f; k2[e] = 0.f; k0[e] = 0.f; }
-    }
+    bn_bwd_table<N>(N * cg, scale, shift, mean, rstd, gamma, dgamma, dbeta, invP, sc, sh, k0, k1, k2);
   };
   struct Off {
     long long x, g1, g2, dx;
@@ -549,22 +505,15 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(View x, PixDiv pd, lo
     float v[N], g1[N], g2[N];
   };
   auto load = [&](const Off& o, In& in) {
-    VW<T>::load(reinterpret_cast<const T*>(x.p) + o.x, in.v);
-    if (gi.has1) VW<T>::load(reinterpret_cast<const T*>(gi.g1.p) + o.g1, in.g1);
-    if (gi.has2) VW<T>::load(reinterpret_cast<const T*>(gi.g2.p) + o.g2, in.g2);
+    Vec16<T>::load(reinterpret_cast<const T*>(x.p) + o.x, in.v);
+    if (gi.has1) Vec16<T>::load(reinterpret_cast<const T*>(gi.g1.p) + o.g1, in.g1);
+    if (gi.has2) Vec16<T>::load(reinterpret_cast<const T*>(gi.g2.p) + o.g2, in.g2);
   };
   auto emit = [&](const Off& o, const In& in) {
     table(o.c / N);
     float d[N];
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-      const float n = fmaf(in.v[e], sc[e], sh[e]);
-      float dn = 0.f;
-      if (gi.has1) dn += in.g1[e] * dact(n, gi.s1);
-      if (gi.has2) dn += in.g2[e] * dact(n, gi.s2);
-      d[e] = fmaf(k1[e], dn, -fmaf(k2[e], in.v[e], k0[e]));
-    }
-    VW<T>::store(reinterpret_cast<T*>(dx.p) + o.dx, d);
+    bn_bwd_dx<N, false>(gi, sc, sh, k0, k1, k2, in.v, in.g1, in.g2, nullptr, d);
+    Vec16<T>::store(reinterpret_cast<T*>(dx.p) + o.dx, d);
   };
   if constexpr (DENSE) {
     // Streaming form (host: every view pixel-dense with 32-bit element offsets, 256 % CG == 0, so
@@ -582,21 +531,14 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(View x, PixDiv pd, lo
     T* dp = reinterpret_cast<T*>(dx.p) + dx.co + c;
     const unsigned xs = x.ps, g1s = gi.g1.ps, g2s = gi.g2.ps, ds = dx.ps;
     auto ld = [&](unsigned q, In& in) {
-      VW<T>::load(xp + q * xs, in.v);
-      if (gi.has1) VW<T>::load(g1p + q * g1s, in.g1);
-      if (gi.has2) VW<T>::load(g2p + q * g2s, in.g2);
+      Vec16<T>::load(xp + q * xs, in.v);
+      if (gi.has1) Vec16<T>::load(g1p + q * g1s, in.g1);
+      if (gi.has2) Vec16<T>::load(g2p + q * g2s, in.g2);
     };
     auto put = [&](unsigned q, const In& in) {
       float d[N];
-#pragma unroll
-      for (int e = 0; e < N; ++e) {
-        const float n = fmaf(in.v[e], sc[e], sh[e]);
-        float dn = 0.f;
-        if (gi.has1) dn += in.g1[e] * dact(n, gi.s1);
-        if (gi.has2) dn += in.g2[e] * dact(n, gi.s2);
-        d[e] = fmaf(k1[e], dn, -fmaf(k2[e], in.v[e], k0[e]));
-      }
-      VW<T>::store(dp + q * ds, d);
+      bn_bwd_dx<N, false>(gi, sc, sh, k0, k1, k2, in.v, in.g1, in.g2, nullptr, d);
+      Vec16<T>::store(dp + q * ds, d);
     };
     for (; pix + pstep < Pu; pix += 2 * pstep) {  // both pixels' loads in flight before either is used
       In a, b;
@@ -629,6 +571,30 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(View x, PixDiv pd, lo
   }
 }
 
+// The forward per element: n = v0*sc + sh, the dropout factor when MASKED (kept: n * keep/(1-p), dropped: 0; it
+// sits between the affine and the activations, in fp32), then y1 = act(n, s1) and optionally y2 = act(n, s2)
+template <typename T, bool MASKED>
+__device__ __forceinline__ void bn_fwd_emit(const float* v0, const float* sc, const float* sh, const float* m,
+                                            const View& y1, long long o1, float s1, const View& y2, long long o2,
+                                            float s2, int has2) {
+  constexpr int N = Vec16<T>::N;
+  float v[N], o[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    const float n = fmaf(v0[e], sc[e], sh[e]);
+    if constexpr (MASKED) v[e] = m[e] != 0.f ? n * m[e] : 0.f;
+    else v[e] = n;
+  }
+#pragma unroll
+  for (int e = 0; e < N; ++e) o[e] = act(v[e], s1);
+  Vec16<T>::store(reinterpret_cast<T*>(y1.p) + o1, o);
+  if (has2) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) o[e] = act(v[e], s2);
+    Vec16<T>::store(reinterpret_cast<T*>(y2.p) + o2, o);
+  }
+}
+
 // Activation materialisation: n = x*scale + shift (identity without a table), then
 // y1 = act(n, slope1) and optionally y2 = act(n, slope2) (slope 0 = ReLU, 0.2 = the
 // LeakyReLU of the reference, 1 = identity).  Applied once per element, so the GEMMs
@@ -638,7 +604,7 @@ template <typename T, bool DENSE>
 __global__ void __launch_bounds__(256) bn_apply_kernel(View x, PixDiv pd, long long P, int C, const float* scale,
                                                        const float* shift, View y1, float s1, View y2, float s2,
                                                        int has2) {
-  constexpr int N = VW<T>::N;
+  constexpr int N = Vec16<T>::N;
   const int CG = C / N;
   const long long total = P * CG;
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -647,11 +613,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(View x, PixDiv pd, long l
   auto table = [&](int cg) {  // this thread's channel group's table, reloaded only when it changes
     if (cg == cg_have) return;
     cg_have = cg;
-    if (scale) { ldc<N>(scale + N * cg, sc); ldc<N>(shift + N * cg, sh); }
-    else {
-#pragma unroll
-      for (int e = 0; e < N; ++e) { sc[e] = 1.f; sh[e] = 0.f; }
-    }
+    ld_affine<N>(scale, shift, N * cg, sc, sh);
   };
   auto offs = [&](long long idx, long long& ox, long long& o1, long long& o2, int& c) {
     const int cg = (int)(idx % CG);
@@ -670,17 +632,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(View x, PixDiv pd, long l
     }
   };
   auto emit = [&](const float* v0, long long o1, long long o2) {
-    float v[N], o[N];
-#pragma unroll
-    for (int e = 0; e < N; ++e) v[e] = fmaf(v0[e], sc[e], sh[e]);
-#pragma unroll
-    for (int e = 0; e < N; ++e) o[e] = act(v[e], s1);
-    VW<T>::store(reinterpret_cast<T*>(y1.p) + o1, o);
-    if (has2) {
-#pragma unroll
-      for (int e = 0; e < N; ++e) o[e] = act(v[e], s2);
-      VW<T>::store(reinterpret_cast<T*>(y2.p) + o2, o);
-    }
+    bn_fwd_emit<T, false>(v0, sc, sh, nullptr, y1, o1, s1, y2, o2, s2, has2);
   };
   if constexpr (DENSE) {  // streaming form: as bn_bwd_apply_kernel's
     const unsigned nthr = gridDim.x * blockDim.x, t0 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -694,14 +646,14 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(View x, PixDiv pd, long l
     const long long b1 = y1.co + c, b2 = y2.co + c;
     for (; pix + pstep < Pu; pix += 2 * pstep) {
       float va[N], vb[N];
-      VW<T>::load(xp + pix * xs, va);
-      VW<T>::load(xp + (pix + pstep) * xs, vb);
+      Vec16<T>::load(xp + pix * xs, va);
+      Vec16<T>::load(xp + (pix + pstep) * xs, vb);
       emit(va, b1 + pix * s1s, b2 + pix * s2s);
       emit(vb, b1 + (pix + pstep) * s1s, b2 + (pix + pstep) * s2s);
     }
     if (pix < Pu) {
       float va[N];
-      VW<T>::load(xp + pix * xs, va);
+      Vec16<T>::load(xp + pix * xs, va);
       emit(va, b1 + pix * s1s, b2 + pix * s2s);
     }
     return;
@@ -713,8 +665,8 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(View x, PixDiv pd, long l
     offs(idx, ax, a1, a2, ca);
     offs(idx + stride, bx, b1, b2, cb);
     float va[N], vb[N];
-    VW<T>::load(reinterpret_cast<const T*>(x.p) + ax, va);
-    VW<T>::load(reinterpret_cast<const T*>(x.p) + bx, vb);
+    Vec16<T>::load(reinterpret_cast<const T*>(x.p) + ax, va);
+    Vec16<T>::load(reinterpret_cast<const T*>(x.p) + bx, vb);
     table(ca / N);
     emit(va, a1, a2);
     table(cb / N);
@@ -725,7 +677,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(View x, PixDiv pd, long l
     int ca;
     offs(idx, ax, a1, a2, ca);
     float va[N];
-    VW<T>::load(reinterpret_cast<const T*>(x.p) + ax, va);
+    Vec16<T>::load(reinterpret_cast<const T*>(x.p) + ax, va);
     table(ca / N);
     emit(va, a1, a2);
   }
@@ -734,38 +686,23 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(View x, PixDiv pd, long l
 // part[chunk][c] = sum over the chunk's pixels of x (conv bias gradients)
 template <typename T>
 __global__ void __launch_bounds__(256) chan_sum_kernel(View x, PixDiv pd, long long P, int C, float* part, int nchunks) {
-  constexpr int N = VW<T>::N;
-  const int CG = C / N;
-  const int RL = 256 / CG;
-  const int cg = threadIdx.x % CG, pl = threadIdx.x / CG;
-  const long long per = (P + nchunks - 1) / nchunks;
-  const long long p0 = blockIdx.x * per, p1 = min(P, p0 + per);
-  __shared__ float red[256][N];
-  float a[N];
+  constexpr int N = Vec16<T>::N;
+  ChunkReduce<N> r(P, C / N, nchunks);
+  const int c = N * r.cg;
+  float acc[N];
 #pragma unroll
-  for (int e = 0; e < N; ++e) a[e] = 0.f;
-  if (pl < RL) {
-    for (long long pix = p0 + pl; pix < p1; pix += RL) {
-      int b, yy, xx;
-      pix_bxy(pd, pix, b, yy, xx);
-      float v[N];
-      VW<T>::load(vptr<T>(x, b, yy, xx, N * cg), v);
+  for (int e = 0; e < N; ++e) acc[e] = 0.f;
+  const bool lead = r.run(acc, [] {}, [&](long long pix) {
+    int b, yy, xx;
+    pix_bxy(pd, pix, b, yy, xx);
+    float v[N];
+    Vec16<T>::load(vptr<T>(x, b, yy, xx, c), v);
 #pragma unroll
-      for (int e = 0; e < N; ++e) a[e] += v[e];
-    }
-  }
+    for (int e = 0; e < N; ++e) acc[e] += v[e];
+  });
+  if (lead) {
 #pragma unroll
-  for (int e = 0; e < N; ++e) red[threadIdx.x][e] = a[e];
-  __syncthreads();
-  if (pl == 0) {
-    float r[N];
-#pragma unroll
-    for (int e = 0; e < N; ++e) r[e] = 0.f;
-    for (int k = 0; k < RL; ++k)
-#pragma unroll
-      for (int e = 0; e < N; ++e) r[e] += red[k * CG + cg][e];
-#pragma unroll
-    for (int e = 0; e < N; ++e) part[(long long)blockIdx.x * C + N * cg + e] = r[e];
+    for (int e = 0; e < N; ++e) part[(long long)blockIdx.x * C + c + e] = acc[e];
   }
 }
 
@@ -792,25 +729,22 @@ static GradIn mkgrad(stc_view g1, float s1, stc_view g2, float s2) {
   return gi;
 }
 
-static int grid_for(long long work) { return (int)std::max<long long>(1, std::min<long long>((work + 255) / 256, 8192)); }
-
 // ---------------------------------------------------------------- dropout (use_dropout=True generators)
-// The mask function lives in philox.hpp; the kernels below are the general-addressing forms of bn_apply_kernel,
-// bn_bwd_reduce_kernel and bn_bwd_apply_kernel with it applied: same thread layout, same reduction order and the
-// same arithmetic per element, so that with every element kept at scale 1 they write what those kernels write.
-// The mask needs (b, y, x) of every vector, and the three tensors it touches are small (<= 8 MB at bs 32): no
-// streaming form.
+// The two element-wise kernels below are the general-addressing forms of bn_apply_kernel and bn_bwd_apply_kernel
+// with the mask applied: the same per-element definitions, so that with every element kept at scale 1 they write
+// what those kernels write.  The mask needs (b, y, x) of every vector, and the tensors it touches are small
+// (<= 8 MB at bs 32): no streaming form.
 
-// y = act(n * keep/(1-p), slope): the dropout sits between the affine and the activation(s), in fp32
+// y = act(n * keep/(1-p), slope)
 template <typename T>
 __global__ void __launch_bounds__(256) bn_apply_drop_kernel(View x, PixDiv pd, long long P, int C, const float* scale,
                                                             const float* shift, View y1, float s1, View y2, float s2,
-                                                            int has2, DropDev drop) {
-  constexpr int N = VW<T>::N;
+                                                            int has2, PhiloxMask mask) {
+  constexpr int N = Vec16<T>::N;
   const int CG = C / N;
   const long long total = P * CG;
   const long long stride = (long long)gridDim.x * blockDim.x;
-  const DropKey key = drop_key(drop);
+  const DropKey key = mask.key();
   struct Off {
     long long x, y1, y2;
     unsigned long long li;  // logical index of the vector's first element
@@ -826,153 +760,58 @@ __global__ void __launch_bounds__(256) bn_apply_drop_kernel(View x, PixDiv pd, l
     o.x = vidx(x, b, yy, xx, o.c);
     o.y1 = vidx(y1, b, yy, xx, o.c);
     o.y2 = vidx(y2, b, yy, xx, o.c);
-    o.li = drop_index(drop, C, b, yy, xx, o.c);
+    o.li = mask.index(C, b, yy, xx, o.c);
     return o;
   };
   auto emit = [&](const Off& o, const float* v0) {
-    float sc[N], sh[N], m[N], v[N], out[N];
-    if (scale) { ldc<N>(scale + o.c, sc); ldc<N>(shift + o.c, sh); }
-    else {
-#pragma unroll
-      for (int e = 0; e < N; ++e) { sc[e] = 1.f; sh[e] = 0.f; }
-    }
-    drop_factor<N>(drop, key, o.li, m);
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-      const float n = fmaf(v0[e], sc[e], sh[e]);
-      v[e] = m[e] != 0.f ? n * m[e] : 0.f;
-    }
-#pragma unroll
-    for (int e = 0; e < N; ++e) out[e] = act(v[e], s1);
-    VW<T>::store(reinterpret_cast<T*>(y1.p) + o.y1, out);
-    if (has2) {
-#pragma unroll
-      for (int e = 0; e < N; ++e) out[e] = act(v[e], s2);
-      VW<T>::store(reinterpret_cast<T*>(y2.p) + o.y2, out);
-    }
+    float sc[N], sh[N], m[N];
+    ld_affine<N>(scale, shift, o.c, sc, sh);
+    mask.template factor<N>(key, o.li, m);
+    bn_fwd_emit<T, true>(v0, sc, sh, m, y1, o.y1, s1, y2, o.y2, s2, has2);
   };
   long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   for (; idx + stride < total; idx += 2 * stride) {  // two 16-byte loads in flight per thread
     const Off oa = offs(idx), ob = offs(idx + stride);
     float va[N], vb[N];
-    VW<T>::load(reinterpret_cast<const T*>(x.p) + oa.x, va);
-    VW<T>::load(reinterpret_cast<const T*>(x.p) + ob.x, vb);
+    Vec16<T>::load(reinterpret_cast<const T*>(x.p) + oa.x, va);
+    Vec16<T>::load(reinterpret_cast<const T*>(x.p) + ob.x, vb);
     emit(oa, va);
     emit(ob, vb);
   }
   if (idx < total) {
     const Off oa = offs(idx);
     float va[N];
-    VW<T>::load(reinterpret_cast<const T*>(x.p) + oa.x, va);
+    Vec16<T>::load(reinterpret_cast<const T*>(x.p) + oa.x, va);
     emit(oa, va);
   }
 }
 
-// bn_bwd_reduce_kernel with g1 * keep/(1-p) (g1 reaches the BN output through the dropout; no mask is stored: it
-// is recomputed from the call's counter): part2[chunk][c] = {sum dn, sum dn*xhat}
-template <typename T>
-__global__ void __launch_bounds__(256) bn_bwd_reduce_drop_kernel(View x, PixDiv pd, long long P, int C,
-                                                                 const float* scale, const float* shift,
-                                                                 const float* mean, const float* rstd, GradIn gi,
-                                                                 float* part, int nchunks, DropDev drop) {
-  constexpr int N = VW<T>::N;
-  const int CG = C / N;
-  const int RL = 256 / CG;
-  const int cg = threadIdx.x % CG, pl = threadIdx.x / CG;
-  const long long per = (P + nchunks - 1) / nchunks;
-  const long long p0 = blockIdx.x * per, p1 = min(P, p0 + per);
-  __shared__ float red[256][2 * N];
-  float a[N], bs[N];
-#pragma unroll
-  for (int e = 0; e < N; ++e) { a[e] = 0.f; bs[e] = 0.f; }
-  if (pl < RL) {
-    const int c = N * cg;
-    const DropKey key = drop_key(drop);
-    float sc[N], shf[N], mu[N], rs[N];
-    ldc<N>(scale + c, sc); ldc<N>(shift + c, shf); ldc<N>(mean + c, mu); ldc<N>(rstd + c, rs);
-    // (4 pixels' loads and Philox rounds in flight together; the sums stay in pixel order, as the plain reduce's)
-#pragma unroll 4
-    for (long long pix = p0 + pl; pix < p1; pix += RL) {
-      int b, yy, xx;
-      pix_bxy(pd, pix, b, yy, xx);
-      float v[N], n[N], g[N], m[N], d[N];
-      VW<T>::load(vptr<T>(x, b, yy, xx, c), v);
-      VW<T>::load(vptr<T>(gi.g1, b, yy, xx, c), g);
-      drop_factor<N>(drop, key, drop_index(drop, C, b, yy, xx, c), m);
-#pragma unroll
-      for (int e = 0; e < N; ++e) {
-        n[e] = fmaf(v[e], sc[e], shf[e]);
-        d[e] = 0.f;
-        d[e] += (g[e] * m[e]) * dact(n[e], gi.s1);
-      }
-      if (gi.has2) {
-        VW<T>::load(vptr<T>(gi.g2, b, yy, xx, c), g);
-#pragma unroll
-        for (int e = 0; e < N; ++e) d[e] += g[e] * dact(n[e], gi.s2);
-      }
-#pragma unroll
-      for (int e = 0; e < N; ++e) {
-        a[e] += d[e];
-        bs[e] += d[e] * (v[e] - mu[e]) * rs[e];
-      }
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < N; ++e) { red[threadIdx.x][e] = a[e]; red[threadIdx.x][N + e] = bs[e]; }
-  __syncthreads();
-  if (pl == 0) {
-    float r0[N], r1[N];
-#pragma unroll
-    for (int e = 0; e < N; ++e) { r0[e] = 0.f; r1[e] = 0.f; }
-    for (int k = 0; k < RL; ++k) {
-      const int t = k * CG + cg;
-#pragma unroll
-      for (int e = 0; e < N; ++e) { r0[e] += red[t][e]; r1[e] += red[t][N + e]; }
-    }
-#pragma unroll
-    for (int e = 0; e < N; ++e)
-      *reinterpret_cast<float2*>(part + ((long long)blockIdx.x * C + N * cg + e) * 2) = make_float2(r0[e], r1[e]);
-  }
-}
-
-// bn_bwd_apply_kernel (with the BN tables) and the same masked g1:
-// dx = k1*dn - k0 - k2*v   with k1 = gamma*rstd, k2 = k1*rstd*dgamma/P, k0 = k1*(dbeta/P - mean*rstd*dgamma/P)
+// bn_bwd_apply_kernel (with the BN tables) and the masked g1
 template <typename T>
 __global__ void __launch_bounds__(256) bn_bwd_apply_drop_kernel(View x, PixDiv pd, long long P, int C,
                                                                 const float* scale, const float* shift,
                                                                 const float* mean, const float* rstd,
                                                                 const float* gamma, GradIn gi, const float* dgamma,
-                                                                const float* dbeta, View dx, DropDev drop) {
-  constexpr int N = VW<T>::N;
+                                                                const float* dbeta, View dx, PhiloxMask mask) {
+  constexpr int N = Vec16<T>::N;
   const int CG = C / N;
   const long long total = P * CG;
   const long long stride = (long long)gridDim.x * blockDim.x;
   const float invP = 1.f / (float)P;
-  const DropKey key = drop_key(drop);
+  const DropKey key = mask.key();
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
     const int c = N * (int)(idx % CG);
     int b, yy, xx;
     pix_bxy(pd, idx / CG, b, yy, xx);
     float v[N], g1[N], g2[N], m[N], d[N];
-    VW<T>::load(vptr<T>(x, b, yy, xx, c), v);
-    VW<T>::load(vptr<T>(gi.g1, b, yy, xx, c), g1);
-    if (gi.has2) VW<T>::load(vptr<T>(gi.g2, b, yy, xx, c), g2);
-    float sc[N], sh[N], mu[N], rs[N], gm[N], dg[N], db[N];
-    ldc<N>(scale + c, sc); ldc<N>(shift + c, sh);
-    ldc<N>(mean + c, mu); ldc<N>(rstd + c, rs); ldc<N>(gamma + c, gm); ldc<N>(dgamma + c, dg); ldc<N>(dbeta + c, db);
-    drop_factor<N>(drop, key, drop_index(drop, C, b, yy, xx, c), m);
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-      const float k1 = gm[e] * rs[e];
-      const float k2 = k1 * rs[e] * dg[e] * invP;
-      const float k0 = k1 * (db[e] * invP - mu[e] * rs[e] * dg[e] * invP);
-      const float n = fmaf(v[e], sc[e], sh[e]);
-      float dn = 0.f;
-      dn += (g1[e] * m[e]) * dact(n, gi.s1);
-      if (gi.has2) dn += g2[e] * dact(n, gi.s2);
-      d[e] = fmaf(k1, dn, -fmaf(k2, v[e], k0));
-    }
-    VW<T>::store(reinterpret_cast<T*>(dx.p) + vidx(dx, b, yy, xx, c), d);
+    Vec16<T>::load(vptr<T>(x, b, yy, xx, c), v);
+    Vec16<T>::load(vptr<T>(gi.g1, b, yy, xx, c), g1);
+    if (gi.has2) Vec16<T>::load(vptr<T>(gi.g2, b, yy, xx, c), g2);
+    float sc[N], sh[N], k0[N], k1[N], k2[N];
+    bn_bwd_table<N, false>(c, scale, shift, mean, rstd, gamma, dgamma, dbeta, invP, sc, sh, k0, k1, k2);
+    mask.template factor<N>(key, mask.index(C, b, yy, xx, c), m);
+    bn_bwd_dx<N, true>(gi, sc, sh, k0, k1, k2, v, g1, g2, m, d);
+    Vec16<T>::store(reinterpret_cast<T*>(dx.p) + vidx(dx, b, yy, xx, c), d);
   }
 }
 
@@ -1022,14 +861,22 @@ static bool vec_ok(int dtype, int C, const stc_view& v) {
   return C % N == 0 && C / N <= 256 && v.cs == 1 && v.co % N == 0 && v.ps % N == 0 && v.rs % N == 0 && v.bs % N == 0;
 }
 
+// what every entry point derives from (dtype, B, x, C): x's device view, its pixel divider, the pixel count and
+// the number of 16-byte channel vectors of all pixels
+struct Pixels {
+  View v;
+  PixDiv pd;
+  long long P, work;
+};
+static Pixels pixels_of(int dtype, int B, const stc_view& x, int C) {
+  const long long P = (long long)B * x.H * x.W;
+  return Pixels{mkview(x), mkpix(B, x.H, x.W), P, P * (C / (dtype == STC_F32 ? 4 : 8))};
+}
+
 extern "C" int stc_chan_stats(int dtype, int B, stc_view x, int C, float* part, int nchunks, void* stream) {
   STC_REQUIRE(vec_ok(dtype, C, x), "stc_chan_stats: C=%d / view not 16-byte vectorisable (NHWC, <= 256 vectors)", C);
-  hipStream_t st = (hipStream_t)stream;
-  View v = mkview(x);
-  const PixDiv pd = mkpix(B, x.H, x.W);
-  const long long P = (long long)B * x.H * x.W;
-  if (dtype == STC_F32) hipLaunchKernelGGL(chan_stats_kernel<float>, dim3(nchunks), dim3(256), 0, st, v, pd, P, C, part, nchunks);
-  else hipLaunchKernelGGL(chan_stats_kernel<bf16>, dim3(nchunks), dim3(256), 0, st, v, pd, P, C, part, nchunks);
+  const Pixels s = pixels_of(dtype, B, x, C);
+  STC_DT(dtype, hipLaunchKernelGGL(chan_stats_kernel<T_>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, s.v, s.pd, s.P, C, part, nchunks));
   STC_CHECK_LAUNCH();
   return 0;
 }
@@ -1040,16 +887,14 @@ extern "C" int stc_bn_apply(int dtype, int B, stc_view x, int C, const float* sc
   STC_REQUIRE(y1.p && vec_ok(dtype, C, x) && vec_ok(dtype, C, y1) && (!y2.p || vec_ok(dtype, C, y2)),
               "stc_bn_apply: C=%d / views not 16-byte vectorisable NHWC", C);
   hipStream_t st = (hipStream_t)stream;
-  View v = mkview(x), o1 = mkview(y1), o2 = y2.p ? mkview(y2) : mkview(y1);
-  const PixDiv pd = mkpix(B, x.H, x.W);
-  const long long P = (long long)B * x.H * x.W;
+  const Pixels s = pixels_of(dtype, B, x, C);
+  View o1 = mkview(y1), o2 = y2.p ? mkview(y2) : mkview(y1);
   const int N = dtype == STC_F32 ? 4 : 8;
   const bool dense = stream_ok(B, x, C, N) && stream_ok(B, y1, C, N) && stream_ok(B, y2, C, N);
-  const int blocks = dense ? grid_stream(P * (C / N)) : grid_for(P * (C / N));
+  const int blocks = dense ? grid_stream(s.work) : grid_for(s.work);
   const int h2 = y2.p != nullptr ? 1 : 0;
-#define STC_BA(T_, D_) hipLaunchKernelGGL((bn_apply_kernel<T_, D_>), dim3(blocks), dim3(256), 0, st, v, pd, P, C, scale, shift, o1, slope1, o2, slope2, h2)
-  if (dtype == STC_F32) { if (dense) STC_BA(float, true); else STC_BA(float, false); }
-  else { if (dense) STC_BA(bf16, true); else STC_BA(bf16, false); }
+#define STC_BA(D_) STC_DT(dtype, hipLaunchKernelGGL((bn_apply_kernel<T_, D_>), dim3(blocks), dim3(256), 0, st, s.v, s.pd, s.P, C, scale, shift, o1, slope1, o2, slope2, h2))
+  if (dense) STC_BA(true); else STC_BA(false);
 #undef STC_BA
   STC_CHECK_LAUNCH();
   return 0;
@@ -1059,11 +904,8 @@ extern "C" int stc_chan_sum(int dtype, int B, stc_view x, int C, int Cout, float
                             void* stream) {
   STC_REQUIRE(vec_ok(dtype, C, x) && Cout <= C, "stc_chan_sum: bad C=%d / view", C);
   hipStream_t st = (hipStream_t)stream;
-  View v = mkview(x);
-  const PixDiv pd = mkpix(B, x.H, x.W);
-  const long long P = (long long)B * x.H * x.W;
-  if (dtype == STC_F32) hipLaunchKernelGGL(chan_sum_kernel<float>, dim3(nchunks), dim3(256), 0, st, v, pd, P, C, part, nchunks);
-  else hipLaunchKernelGGL(chan_sum_kernel<bf16>, dim3(nchunks), dim3(256), 0, st, v, pd, P, C, part, nchunks);
+  const Pixels s = pixels_of(dtype, B, x, C);
+  STC_DT(dtype, hipLaunchKernelGGL(chan_sum_kernel<T_>, dim3(nchunks), dim3(256), 0, st, s.v, s.pd, s.P, C, part, nchunks));
   STC_CHECK_LAUNCH();
   hipLaunchKernelGGL(chan_sum_final_kernel, dim3(C), dim3(256), 0, st, (const float*)part, nchunks, C, Cout, out);
   STC_CHECK_LAUNCH();
@@ -1080,13 +922,10 @@ extern "C" int stc_bn_finalize(const float* part, int nchunks, int C, const floa
     hipLaunchKernelGGL(bn_eval_table_kernel, dim3((C + 255) / 256), dim3(256), 0, st, C, gamma, beta, running_mean,
                        running_var, eps, scale, shift);
   } else {
-    if (nchunks <= 1024)  // up to 4 load groups per lane in registers; more chunks: a block per channel
-      hipLaunchKernelGGL(bn_finalize_wave_kernel, dim3((C + 3) / 4), dim3(256), 0, st, part, nchunks, C, gamma, beta,
-                         running_mean, running_var, (long long*)num_batches_tracked, momentum, eps, mean, rstd, scale,
-                         shift);
-    else
-      hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, st, part, nchunks, C, gamma, beta, running_mean,
-                         running_var, (long long*)num_batches_tracked, momentum, eps, mean, rstd, scale, shift);
+#define STC_BF(R_) hipLaunchKernelGGL(bn_finalize_kernel<R_>, merge_grid<R_>(C), dim3(256), 0, st, part, nchunks, C, gamma, beta, running_mean, running_var, (long long*)num_batches_tracked, momentum, eps, mean, rstd, scale, shift)
+    // up to 4 load groups per lane in registers; more chunks: a block per channel
+    if (nchunks <= 1024) STC_BF(WaveMerge); else STC_BF(BlockMerge);
+#undef STC_BF
   }
   STC_CHECK_LAUNCH();
   return 0;
@@ -1098,17 +937,20 @@ extern "C" int stc_bn_bwd_reduce(int dtype, int B, stc_view x, int C, const floa
   STC_REQUIRE(vec_ok(dtype, C, x) && (!g1.p || vec_ok(dtype, C, g1)) && (!g2.p || vec_ok(dtype, C, g2)),
               "stc_bn_bwd_reduce: bad C=%d / views", C);
   STC_REQUIRE(scale && shift && mean && rstd, "stc_bn_bwd_reduce: BN tables required");
-  hipStream_t st = (hipStream_t)stream;
   GradIn gi = mkgrad(g1, slope1, g2, slope2);
-  View v = mkview(x);
-  const PixDiv pd = mkpix(B, x.H, x.W);
-  const long long P = (long long)B * x.H * x.W;
-  if (dtype == STC_F32)
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(nchunks), dim3(256), 0, st, v, pd, P, C, scale, shift, mean, rstd, gi, part2, nchunks);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16>, dim3(nchunks), dim3(256), 0, st, v, pd, P, C, scale, shift, mean, rstd, gi, part2, nchunks);
+  const Pixels s = pixels_of(dtype, B, x, C);
+  STC_DT(dtype, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T_, NoMask>), dim3(nchunks), dim3(256), 0, (hipStream_t)stream, s.v, s.pd, s.P, C, scale, shift, mean, rstd, gi, part2, nchunks, NoMask{}));
   STC_CHECK_LAUNCH();
   return 0;
+}
+
+// dgamma / dbeta from the backward reduce's partials: a wave per channel while a lane's one load group covers
+// the chunks, else a block per channel
+static void bwd_finalize(const float* part2, int nchunks, int C, float* dgamma, float* dbeta, hipStream_t st) {
+  if (nchunks <= 256)
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<WaveMerge>, merge_grid<WaveMerge>(C), dim3(256), 0, st, part2, nchunks, C, dgamma, dbeta);
+  else
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<BlockMerge>, merge_grid<BlockMerge>(C), dim3(256), 0, st, part2, nchunks, C, dgamma, dbeta);
 }
 
 extern "C" int stc_bn_bwd_apply(int dtype, int B, stc_view x, int C, const float* scale, const float* shift,
@@ -1122,22 +964,16 @@ extern "C" int stc_bn_bwd_apply(int dtype, int B, stc_view x, int C, const float
   GradIn gi = mkgrad(g1, slope1, g2, slope2);
   if (mean) {
     STC_REQUIRE(part2 && dgamma && dbeta && gamma && rstd && scale && shift, "stc_bn_bwd_apply: missing BN tensors");
-    if (nchunks <= 256)
-      hipLaunchKernelGGL(bn_bwd_finalize_wave_kernel, dim3((C + 3) / 4), dim3(256), 0, st, part2, nchunks, C, dgamma, dbeta);
-    else
-      hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, part2, nchunks, C, dgamma, dbeta);
+    bwd_finalize(part2, nchunks, C, dgamma, dbeta, st);
     STC_CHECK_LAUNCH();
   }
-  View v = mkview(x), o = mkview(dx);
-  const PixDiv pd = mkpix(B, x.H, x.W);
-  const long long P = (long long)B * x.H * x.W;
+  const Pixels s = pixels_of(dtype, B, x, C);
+  View o = mkview(dx);
   const int N = dtype == STC_F32 ? 4 : 8;
-  const long long work = P * (C / N);
   const bool dense = stream_ok(B, x, C, N) && stream_ok(B, dx, C, N) && stream_ok(B, g1, C, N) && stream_ok(B, g2, C, N);
-  const int blocks = dense ? grid_stream(work) : grid_for(work);
-#define STC_BB(T_, D_) hipLaunchKernelGGL((bn_bwd_apply_kernel<T_, D_>), dim3(blocks), dim3(256), 0, st, v, pd, P, C, scale, shift, mean, rstd, gamma, gi, dgamma, dbeta, o)
-  if (dtype == STC_F32) { if (dense) STC_BB(float, true); else STC_BB(float, false); }
-  else { if (dense) STC_BB(bf16, true); else STC_BB(bf16, false); }
+  const int blocks = dense ? grid_stream(s.work) : grid_for(s.work);
+#define STC_BB(D_) STC_DT(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T_, D_>), dim3(blocks), dim3(256), 0, st, s.v, s.pd, s.P, C, scale, shift, mean, rstd, gamma, gi, dgamma, dbeta, o))
+  if (dense) STC_BB(true); else STC_BB(false);
 #undef STC_BB
   STC_CHECK_LAUNCH();
   return 0;
@@ -1182,21 +1018,15 @@ extern "C" int stc_bn_apply_drop(int dtype, int B, stc_view x, int C, const floa
   STC_REQUIRE((scale == nullptr) == (shift == nullptr), "stc_bn_apply_drop: scale/shift must come together");
   STC_REQUIRE(y1.p && vec_ok(dtype, C, x) && vec_ok(dtype, C, y1) && (!y2.p || vec_ok(dtype, C, y2)),
               "stc_bn_apply_drop: C=%d / views not 16-byte vectorisable NHWC", C);
-  DropDev dd;
-  if (int rc = mkdrop(drop, B, C, &dd, "stc_bn_apply_drop")) return rc;
+  PhiloxMask mask;
+  if (int rc = mkdrop(drop, B, C, &mask.d, "stc_bn_apply_drop")) return rc;
   STC_REQUIRE(x.H <= drop->H && x.W <= drop->W, "stc_bn_apply_drop: view %d x %d outside the dropout extent %d x %d",
               x.H, x.W, drop->H, drop->W);
-  hipStream_t st = (hipStream_t)stream;
-  View v = mkview(x), o1 = mkview(y1), o2 = y2.p ? mkview(y2) : mkview(y1);
-  const PixDiv pd = mkpix(B, x.H, x.W);
-  const long long P = (long long)B * x.H * x.W;
-  const int N = dtype == STC_F32 ? 4 : 8;
-  const int blocks = grid_for(P * (C / N));  // covers the tensor once at the generator's sizes (launch-latency bound)
+  const Pixels s = pixels_of(dtype, B, x, C);
+  View o1 = mkview(y1), o2 = y2.p ? mkview(y2) : mkview(y1);
+  const int blocks = grid_for(s.work);  // covers the tensor once at the generator's sizes (launch-latency bound)
   const int h2 = y2.p != nullptr ? 1 : 0;
-  if (dtype == STC_F32)
-    hipLaunchKernelGGL(bn_apply_drop_kernel<float>, dim3(blocks), dim3(256), 0, st, v, pd, P, C, scale, shift, o1, slope1, o2, slope2, h2, dd);
-  else
-    hipLaunchKernelGGL(bn_apply_drop_kernel<bf16>, dim3(blocks), dim3(256), 0, st, v, pd, P, C, scale, shift, o1, slope1, o2, slope2, h2, dd);
+  STC_DT(dtype, hipLaunchKernelGGL(bn_apply_drop_kernel<T_>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, s.v, s.pd, s.P, C, scale, shift, o1, slope1, o2, slope2, h2, mask));
   STC_CHECK_LAUNCH();
   return 0;
 }
@@ -1236,18 +1066,12 @@ extern "C" int stc_bn_bwd_reduce_drop(int dtype, int B, stc_view x, int C, const
   STC_REQUIRE(vec_ok(dtype, C, x) && g1.p && vec_ok(dtype, C, g1) && (!g2.p || vec_ok(dtype, C, g2)),
               "stc_bn_bwd_reduce_drop: bad C=%d / views (g1 required)", C);
   STC_REQUIRE(scale && shift && mean && rstd, "stc_bn_bwd_reduce_drop: BN tables required");
-  DropDev dd;
-  if (int rc = mkdrop(drop, B, C, &dd, "stc_bn_bwd_reduce_drop")) return rc;
+  PhiloxMask mask;
+  if (int rc = mkdrop(drop, B, C, &mask.d, "stc_bn_bwd_reduce_drop")) return rc;
   STC_REQUIRE(x.H <= drop->H && x.W <= drop->W, "stc_bn_bwd_reduce_drop: view outside the dropout extent");
-  hipStream_t st = (hipStream_t)stream;
   GradIn gi = mkgrad(g1, slope1, g2, slope2);
-  View v = mkview(x);
-  const PixDiv pd = mkpix(B, x.H, x.W);
-  const long long P = (long long)B * x.H * x.W;
-  if (dtype == STC_F32)
-    hipLaunchKernelGGL(bn_bwd_reduce_drop_kernel<float>, dim3(nchunks), dim3(256), 0, st, v, pd, P, C, scale, shift, mean, rstd, gi, part2, nchunks, dd);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_drop_kernel<bf16>, dim3(nchunks), dim3(256), 0, st, v, pd, P, C, scale, shift, mean, rstd, gi, part2, nchunks, dd);
+  const Pixels s = pixels_of(dtype, B, x, C);
+  STC_DT(dtype, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T_, PhiloxMask>), dim3(nchunks), dim3(256), 0, (hipStream_t)stream, s.v, s.pd, s.P, C, scale, shift, mean, rstd, gi, part2, nchunks, mask));
   STC_CHECK_LAUNCH();
   return 0;
 }
@@ -1262,25 +1086,16 @@ extern "C" int stc_bn_bwd_apply_drop(int dtype, int B, stc_view x, int C, const 
               "stc_bn_bwd_apply_drop: bad C=%d / views (g1 required)", C);
   STC_REQUIRE(mean && part2 && nchunks > 0 && dgamma && dbeta && gamma && rstd && scale && shift,
               "stc_bn_bwd_apply_drop: missing BN tensors");
-  DropDev dd;
-  if (int rc = mkdrop(drop, B, C, &dd, "stc_bn_bwd_apply_drop")) return rc;
+  PhiloxMask mask;
+  if (int rc = mkdrop(drop, B, C, &mask.d, "stc_bn_bwd_apply_drop")) return rc;
   STC_REQUIRE(x.H <= drop->H && x.W <= drop->W, "stc_bn_bwd_apply_drop: view outside the dropout extent");
   hipStream_t st = (hipStream_t)stream;
   GradIn gi = mkgrad(g1, slope1, g2, slope2);
-  if (nchunks <= 256)
-    hipLaunchKernelGGL(bn_bwd_finalize_wave_kernel, dim3((C + 3) / 4), dim3(256), 0, st, part2, nchunks, C, dgamma, dbeta);
-  else
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, part2, nchunks, C, dgamma, dbeta);
+  bwd_finalize(part2, nchunks, C, dgamma, dbeta, st);
   STC_CHECK_LAUNCH();
-  View v = mkview(x), o = mkview(dx);
-  const PixDiv pd = mkpix(B, x.H, x.W);
-  const long long P = (long long)B * x.H * x.W;
-  const int N = dtype == STC_F32 ? 4 : 8;
-  const int blocks = grid_for(P * (C / N));
-  if (dtype == STC_F32)
-    hipLaunchKernelGGL(bn_bwd_apply_drop_kernel<float>, dim3(blocks), dim3(256), 0, st, v, pd, P, C, scale, shift, mean, rstd, gamma, gi, dgamma, dbeta, o, dd);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_drop_kernel<bf16>, dim3(blocks), dim3(256), 0, st, v, pd, P, C, scale, shift, mean, rstd, gamma, gi, dgamma, dbeta, o, dd);
+  const Pixels s = pixels_of(dtype, B, x, C);
+  View o = mkview(dx);
+  STC_DT(dtype, hipLaunchKernelGGL(bn_bwd_apply_drop_kernel<T_>, dim3(grid_for(s.work)), dim3(256), 0, st, s.v, s.pd, s.P, C, scale, shift, mean, rstd, gamma, gi, dgamma, dbeta, o, mask));
   STC_CHECK_LAUNCH();
   return 0;
 }

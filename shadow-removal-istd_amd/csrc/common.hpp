@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
+#include <algorithm>
 #include <string>
 #include <cstdio>
 #include <cstdarg>
@@ -57,6 +58,13 @@ void main_timer_end(hipStream_t st);
 #define STC_REQUIRE(cond, ...)                                                 \
   do {                                                                         \
     if (!(cond)) return ::stc::fail(-1, __VA_ARGS__);                          \
+  } while (0)
+
+// runs the statement with T_ = float (STC_F32) or bf16: STC_DT(dtype, hipLaunchKernelGGL((k<T_>), ...))
+#define STC_DT(dtype_, ...)                                                    \
+  do {                                                                         \
+    if ((dtype_) == STC_F32) { using T_ = float; __VA_ARGS__; }                \
+    else { using T_ = ::stc::bf16; __VA_ARGS__; }                              \
   } while (0)
 
 // ---------------------------------------------------------------- bf16 helpers
@@ -133,6 +141,15 @@ __device__ __forceinline__ float act(float v, float slope) { return v > 0.f ? v 
 __device__ __forceinline__ float dact(float n, float slope) { return n > 0.f ? 1.f : slope; }
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// blocks of 256 threads for a grid-stride loop over `work` items
+static inline int grid_for(long long work) { return (int)std::max<long long>(1, std::min<long long>((work + 255) / 256, 8192)); }
+
+// fp64 butterfly over the 64 lanes of a wave: every lane gets the same total, in a fixed order
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 // q = n / d for 0 <= n < 2^24, d >= 1, with inv = 1.0f / d from the host: the float estimate is
 // within one of the quotient, one integer correction makes it exact (≈6 VALU instead of the ≈35 of a

@@ -352,8 +352,6 @@ __global__ void pack_kernel(int mode, const float* W, int P, int Q, T* out, int 
   }
 }
 
-static int grid_for(long long work) { return (int)std::max<long long>(1, std::min<long long>((work + 255) / 256, 8192)); }
-
 }  // namespace stc
 
 using namespace stc;

@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "vec16.hpp"
 
 namespace stc {
 namespace inorm {
@@ -34,52 +35,17 @@ constexpr int KV = 8;         // 16-byte vectors per thread (x; the backward als
 #endif
 constexpr int SV_MAX = STC_IN_SLAB_VECS;
 
-template <typename T> struct VT;
-template <> struct VT<float> {
-  static constexpr int N = 4;
-  __device__ __forceinline__ static void unpack(const uint4& v, float* f) {
-    f[0] = __uint_as_float(v.x); f[1] = __uint_as_float(v.y); f[2] = __uint_as_float(v.z); f[3] = __uint_as_float(v.w);
-  }
-  __device__ __forceinline__ static uint4 pack(const float* f) {
-    return make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
-  }
-};
-template <> struct VT<bf16> {
-  static constexpr int N = 8;
-  __device__ __forceinline__ static void unpack(const uint4& v, float* f) {
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { f[2 * q] = __uint_as_float(w[q] << 16); f[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u); }
-  }
-  __device__ __forceinline__ static uint4 pack(const float* f) {  // round-to-nearest-even, as stc_bn_apply
-    uint4 v;
-    v.x = (unsigned)f2bf(f[0]) | ((unsigned)f2bf(f[1]) << 16);
-    v.y = (unsigned)f2bf(f[2]) | ((unsigned)f2bf(f[3]) << 16);
-    v.z = (unsigned)f2bf(f[4]) | ((unsigned)f2bf(f[5]) << 16);
-    v.w = (unsigned)f2bf(f[6]) | ((unsigned)f2bf(f[7]) << 16);
-    return v;
-  }
-};
-
 template <typename T>
 __device__ __forceinline__ uint4 ldv(const View& v, int b, int y, int x, int c) {
-  return *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(v.p) + vidx(v, b, y, x, c));
+  return Vec16<T>::ldraw(reinterpret_cast<const T*>(v.p) + vidx(v, b, y, x, c));
 }
 template <typename T>
 __device__ __forceinline__ void stv(const View& v, int b, int y, int x, int c, const uint4& u) {
-  *reinterpret_cast<uint4*>(reinterpret_cast<T*>(v.p) + vidx(v, b, y, x, c)) = u;
-}
-template <int N>
-__device__ __forceinline__ void ldf(const float* p, float* f) {
-#pragma unroll
-  for (int e = 0; e < N; e += 4) {
-    const float4 v = *reinterpret_cast<const float4*>(p + e);
-    f[e] = v.x; f[e + 1] = v.y; f[e + 2] = v.z; f[e + 3] = v.w;
-  }
+  Vec16<T>::straw(reinterpret_cast<T*>(v.p) + vidx(v, b, y, x, c), u);
 }
 template <int N>
 __device__ __forceinline__ void affine_of(const float* gamma, const float* beta, int c, float* ga, float* be) {
-  if (gamma) { ldf<N>(gamma + c, ga); ldf<N>(beta + c, be); }
+  if (gamma) { ldc<N>(gamma + c, ga); ldc<N>(beta + c, be); }
   else {
 #pragma unroll
     for (int e = 0; e < N; ++e) { ga[e] = 1.f; be[e] = 0.f; }
@@ -156,11 +122,11 @@ __device__ __forceinline__ void emit(const Outs& o, int b, int y, int x, int c, 
   for (int e = 0; e < N; ++e) n[e] = fmaf((f[e] - mu[e]) * rs[e], ga[e], be[e]);
 #pragma unroll
   for (int e = 0; e < N; ++e) r[e] = act(n[e], o.s1);
-  stv<T>(o.y1, b, y, x, c, VT<T>::pack(r));
+  stv<T>(o.y1, b, y, x, c, Vec16<T>::pack(r));
   if (o.has2) {
 #pragma unroll
     for (int e = 0; e < N; ++e) r[e] = act(n[e], o.s2);
-    stv<T>(o.y2, b, y, x, c, VT<T>::pack(r));
+    stv<T>(o.y2, b, y, x, c, Vec16<T>::pack(r));
   }
 }
 
@@ -170,9 +136,9 @@ __device__ __forceinline__ void dn_xhat(const Grads& gr, const uint4& xr, const 
                                         const float* mu, const float* rs, const float* ga, const float* be, float* dn,
                                         float* xh) {
   float f[N], a[N], q[N];
-  VT<T>::unpack(xr, f);
-  VT<T>::unpack(ar, a);
-  VT<T>::unpack(br, q);
+  Vec16<T>::unpack(xr, f);
+  Vec16<T>::unpack(ar, a);
+  Vec16<T>::unpack(br, q);
 #pragma unroll
   for (int e = 0; e < N; ++e) {
     xh[e] = (f[e] - mu[e]) * rs[e];
@@ -188,7 +154,7 @@ __device__ __forceinline__ void dn_xhat(const Grads& gr, const uint4& xr, const 
 template <typename T>
 __global__ void __launch_bounds__(TINY_NT) in_fwd_tiny_kernel(View x, Geo g, int B, const float* gamma, const float* beta,
                                                               float eps, float* mean, float* rstd, Outs o) {
-  constexpr int N = VT<T>::N;
+  constexpr int N = Vec16<T>::N;
   const long long t = (long long)blockIdx.x * TINY_NT + threadIdx.x;
   if (t >= (long long)B * g.CG) return;
   const int b = (int)(t / g.CG), c = N * (int)(t % g.CG);
@@ -197,14 +163,14 @@ __global__ void __launch_bounds__(TINY_NT) in_fwd_tiny_kernel(View x, Geo g, int
   for (int j = 0; j < TINY_MAX; ++j)
     if (j < g.P) r[j] = ldv<T>(x, b, j / g.W, j % g.W, c);
   float sh[N], s[N], mu[N], q[N], rs[N], ga[N], be[N];
-  VT<T>::unpack(r[0], sh);
+  Vec16<T>::unpack(r[0], sh);
 #pragma unroll
   for (int e = 0; e < N; ++e) { s[e] = 0.f; q[e] = 0.f; }
 #pragma unroll
   for (int j = 0; j < TINY_MAX; ++j)
     if (j < g.P) {
       float f[N];
-      VT<T>::unpack(r[j], f);
+      Vec16<T>::unpack(r[j], f);
 #pragma unroll
       for (int e = 0; e < N; ++e) s[e] += f[e] - sh[e];
     }
@@ -214,7 +180,7 @@ __global__ void __launch_bounds__(TINY_NT) in_fwd_tiny_kernel(View x, Geo g, int
   for (int j = 0; j < TINY_MAX; ++j)
     if (j < g.P) {
       float f[N];
-      VT<T>::unpack(r[j], f);
+      Vec16<T>::unpack(r[j], f);
 #pragma unroll
       for (int e = 0; e < N; ++e) { const float d = f[e] - mu[e]; q[e] = fmaf(d, d, q[e]); }
     }
@@ -231,7 +197,7 @@ __global__ void __launch_bounds__(TINY_NT) in_fwd_tiny_kernel(View x, Geo g, int
       const int y = j / g.W, xx = j % g.W;
       if (y < o.Ha && xx < o.Wa) {
         float f[N];
-        VT<T>::unpack(r[j], f);
+        Vec16<T>::unpack(r[j], f);
         emit<T, N>(o, b, y, xx, c, f, mu, rs, ga, be);
       }
     }
@@ -241,13 +207,13 @@ template <typename T>
 __global__ void __launch_bounds__(TINY_NT) in_bwd_tiny_kernel(View x, Geo g, int B, const float* gamma, const float* beta,
                                                               const float* mean, const float* rstd, Grads gr, View dx,
                                                               float* sums) {
-  constexpr int N = VT<T>::N;
+  constexpr int N = Vec16<T>::N;
   const long long t = (long long)blockIdx.x * TINY_NT + threadIdx.x;
   if (t >= (long long)B * g.CG) return;
   const int b = (int)(t / g.CG), c = N * (int)(t % g.CG);
   float mu[N], rs[N], ga[N], be[N], A[N], Bs[N];
-  ldf<N>(mean + (long long)b * g.C + c, mu);
-  ldf<N>(rstd + (long long)b * g.C + c, rs);
+  ldc<N>(mean + (long long)b * g.C + c, mu);
+  ldc<N>(rstd + (long long)b * g.C + c, rs);
   affine_of<N>(gamma, beta, c, ga, be);
 #pragma unroll
   for (int e = 0; e < N; ++e) { A[e] = 0.f; Bs[e] = 0.f; }
@@ -279,10 +245,10 @@ __global__ void __launch_bounds__(TINY_NT) in_bwd_tiny_kernel(View x, Geo g, int
   for (int j = 0; j < TINY_MAX; ++j)
     if (j < g.P) {
       float f[N], d[N];
-      VT<T>::unpack(r[j], f);
+      Vec16<T>::unpack(r[j], f);
 #pragma unroll
       for (int e = 0; e < N; ++e) d[e] = k[e] * (dnr[j][e] - A[e] - (f[e] - mu[e]) * rs[e] * Bs[e]);
-      stv<T>(dx, b, j / g.W, j % g.W, c, VT<T>::pack(d));
+      stv<T>(dx, b, j / g.W, j % g.W, c, Vec16<T>::pack(d));
     }
 }
 
@@ -292,7 +258,7 @@ __global__ void __launch_bounds__(TINY_NT) in_bwd_tiny_kernel(View x, Geo g, int
 template <typename T, int MODE>
 __global__ void __launch_bounds__(NT) in_fwd_kernel(View x, Geo g, const float* gamma, const float* beta, float eps,
                                                     float* mean, float* rstd, Outs o, float* part) {
-  constexpr int N = VT<T>::N;
+  constexpr int N = Vec16<T>::N;
   __shared__ float red[NT * N];
   const int tid = threadIdx.x, cgl = tid % g.SV, pl = tid / g.SV;
   const int cg = blockIdx.y * g.SV + cgl, b = blockIdx.z, ch = blockIdx.x;
@@ -310,12 +276,12 @@ __global__ void __launch_bounds__(NT) in_fwd_kernel(View x, Geo g, const float* 
     float sh[N], s[N], q[N];
 #pragma unroll
     for (int e = 0; e < N; ++e) { sh[e] = 0.f; s[e] = 0.f; q[e] = 0.f; }
-    if (on) VT<T>::unpack(ldv<T>(x, b, p0 / g.W, p0 % g.W, c), sh);  // the chunk's first pixel: the shift
+    if (on) Vec16<T>::unpack(ldv<T>(x, b, p0 / g.W, p0 % g.W, c), sh);  // the chunk's first pixel: the shift
 #pragma unroll
     for (int j = 0; j < KV; ++j)
       if (on && p0 + pl + j * g.RL < p1) {
         float f[N];
-        VT<T>::unpack(r[j], f);
+        Vec16<T>::unpack(r[j], f);
 #pragma unroll
         for (int e = 0; e < N; ++e) s[e] += f[e] - sh[e];
       }
@@ -327,7 +293,7 @@ __global__ void __launch_bounds__(NT) in_fwd_kernel(View x, Geo g, const float* 
     for (int j = 0; j < KV; ++j)
       if (on && p0 + pl + j * g.RL < p1) {
         float f[N];
-        VT<T>::unpack(r[j], f);
+        Vec16<T>::unpack(r[j], f);
 #pragma unroll
         for (int e = 0; e < N; ++e) { const float d = f[e] - mu[e]; q[e] = fmaf(d, d, q[e]); }
       }
@@ -352,7 +318,7 @@ __global__ void __launch_bounds__(NT) in_fwd_kernel(View x, Geo g, const float* 
         const double nk = (double)(min(g.P, (k + 1) * g.pc) - k * g.pc);
         const double tot = cnt + nk, w = nk / tot;
         float pv[2 * N];
-        ldf<2 * N>(part + (((long long)b * g.nchunks + k) * g.C + c) * 2, pv);
+        ldc<2 * N>(part + (((long long)b * g.nchunks + k) * g.C + c) * 2, pv);
 #pragma unroll
         for (int e = 0; e < N; ++e) {
           const double d = (double)pv[2 * e] - M[e];
@@ -388,7 +354,7 @@ __global__ void __launch_bounds__(NT) in_fwd_kernel(View x, Geo g, const float* 
       const int y = pix / g.W, xx = pix % g.W;
       if (y < o.Ha && xx < o.Wa) {
         float f[N];
-        VT<T>::unpack(r[j], f);
+        Vec16<T>::unpack(r[j], f);
         emit<T, N>(o, b, y, xx, c, f, mu, rs, ga, be);
       }
     }
@@ -401,7 +367,7 @@ template <typename T, int MODE>
 __global__ void __launch_bounds__(NT) in_bwd_kernel(View x, Geo g, const float* gamma, const float* beta,
                                                     const float* mean, const float* rstd, Grads gr, View dx, float* part,
                                                     float* sums) {
-  constexpr int N = VT<T>::N;
+  constexpr int N = Vec16<T>::N;
   __shared__ float red[NT * 2 * N];
   const int tid = threadIdx.x, cgl = tid % g.SV, pl = tid / g.SV;
   const int cg = blockIdx.y * g.SV + cgl, b = blockIdx.z, ch = blockIdx.x;
@@ -424,8 +390,8 @@ __global__ void __launch_bounds__(NT) in_bwd_kernel(View x, Geo g, const float* 
 #pragma unroll
   for (int e = 0; e < N; ++e) { mu[e] = 0.f; rs[e] = 0.f; ga[e] = 1.f; be[e] = 0.f; }
   if (on) {
-    ldf<N>(mean + (long long)b * g.C + c, mu);
-    ldf<N>(rstd + (long long)b * g.C + c, rs);
+    ldc<N>(mean + (long long)b * g.C + c, mu);
+    ldc<N>(rstd + (long long)b * g.C + c, rs);
     affine_of<N>(gamma, beta, c, ga, be);
   }
 #pragma unroll
@@ -452,7 +418,7 @@ __global__ void __launch_bounds__(NT) in_bwd_kernel(View x, Geo g, const float* 
     if (on && pl == 0) {
       for (int k = 0; k < g.nchunks; ++k) {  // chunk order
         float pv[2 * N];
-        ldf<2 * N>(part + (((long long)b * g.nchunks + k) * g.C + c) * 2, pv);
+        ldc<2 * N>(part + (((long long)b * g.nchunks + k) * g.C + c) * 2, pv);
 #pragma unroll
         for (int e = 0; e < N; ++e) { S[e] += pv[2 * e]; S[N + e] += pv[2 * e + 1]; }
       }
@@ -480,7 +446,7 @@ __global__ void __launch_bounds__(NT) in_bwd_kernel(View x, Geo g, const float* 
       dn_xhat<T, N>(gr, r[j], a[j], q[j], mu, rs, ga, be, dn, xh);
 #pragma unroll
       for (int e = 0; e < N; ++e) d[e] = k[e] * (dn[e] - S[e] - xh[e] * S[N + e]);
-      stv<T>(dx, b, pix / g.W, pix % g.W, c, VT<T>::pack(d));
+      stv<T>(dx, b, pix / g.W, pix % g.W, c, Vec16<T>::pack(d));
     }
   }
 }
@@ -608,21 +574,20 @@ extern "C" int stc_in_fwd(int dtype, int B, stc_view x, int C, const float* gamm
   const Geo& g = p.g;
   if (p.regime == 0) {
     const int blocks = cdiv((long long)B * g.CG, TINY_NT);
-    if (dtype == STC_F32) hipLaunchKernelGGL(in_fwd_tiny_kernel<float>, dim3(blocks), dim3(TINY_NT), 0, st, v, g, B, gamma, beta, eps, mean, rstd, o);
-    else hipLaunchKernelGGL(in_fwd_tiny_kernel<bf16>, dim3(blocks), dim3(TINY_NT), 0, st, v, g, B, gamma, beta, eps, mean, rstd, o);
+    STC_DT(dtype, hipLaunchKernelGGL(in_fwd_tiny_kernel<T_>, dim3(blocks), dim3(TINY_NT), 0, st, v, g, B, gamma, beta, eps, mean, rstd, o));
     STC_CHECK_LAUNCH();
     return 0;
   }
   const dim3 grid(g.nchunks, p.nslab, B);
-#define STC_INF(T_, M_) hipLaunchKernelGGL((in_fwd_kernel<T_, M_>), grid, dim3(NT), 0, st, v, g, gamma, beta, eps, mean, rstd, o, part)
+#define STC_INF(M_) STC_DT(dtype, hipLaunchKernelGGL((in_fwd_kernel<T_, M_>), grid, dim3(NT), 0, st, v, g, gamma, beta, eps, mean, rstd, o, part))
   if (p.regime == 1) {
-    if (dtype == STC_F32) STC_INF(float, 0); else STC_INF(bf16, 0);
+    STC_INF(0);
     STC_CHECK_LAUNCH();
     return 0;
   }
-  if (dtype == STC_F32) STC_INF(float, 1); else STC_INF(bf16, 1);
+  STC_INF(1);
   STC_CHECK_LAUNCH();
-  if (dtype == STC_F32) STC_INF(float, 2); else STC_INF(bf16, 2);
+  STC_INF(2);
 #undef STC_INF
   STC_CHECK_LAUNCH();
   return 0;
@@ -655,18 +620,17 @@ extern "C" int stc_in_bwd(int dtype, int B, stc_view x, int C, const float* gamm
   const Geo& g = p.g;
   if (p.regime == 0) {
     const int blocks = cdiv((long long)B * g.CG, TINY_NT);
-    if (dtype == STC_F32) hipLaunchKernelGGL(in_bwd_tiny_kernel<float>, dim3(blocks), dim3(TINY_NT), 0, st, v, g, B, gamma, beta, mean, rstd, gr, o, sums);
-    else hipLaunchKernelGGL(in_bwd_tiny_kernel<bf16>, dim3(blocks), dim3(TINY_NT), 0, st, v, g, B, gamma, beta, mean, rstd, gr, o, sums);
+    STC_DT(dtype, hipLaunchKernelGGL(in_bwd_tiny_kernel<T_>, dim3(blocks), dim3(TINY_NT), 0, st, v, g, B, gamma, beta, mean, rstd, gr, o, sums));
     STC_CHECK_LAUNCH();
   } else {
     const dim3 grid(g.nchunks, p.nslab, B);
-#define STC_INB(T_, M_) hipLaunchKernelGGL((in_bwd_kernel<T_, M_>), grid, dim3(NT), 0, st, v, g, gamma, beta, mean, rstd, gr, o, part, sums)
+#define STC_INB(M_) STC_DT(dtype, hipLaunchKernelGGL((in_bwd_kernel<T_, M_>), grid, dim3(NT), 0, st, v, g, gamma, beta, mean, rstd, gr, o, part, sums))
     if (p.regime == 1) {
-      if (dtype == STC_F32) STC_INB(float, 0); else STC_INB(bf16, 0);
+      STC_INB(0);
     } else {
-      if (dtype == STC_F32) STC_INB(float, 1); else STC_INB(bf16, 1);
+      STC_INB(1);
       STC_CHECK_LAUNCH();
-      if (dtype == STC_F32) STC_INB(float, 2); else STC_INB(bf16, 2);
+      STC_INB(2);
     }
 #undef STC_INB
     STC_CHECK_LAUNCH();

@@ -37,12 +37,6 @@ __device__ __forceinline__ void rgb2lab(float r, float g, float b, float* lab) {
   lab[2] = 200.f * (fy - fz);
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ void __launch_bounds__(256) istd_errors_kernel(const unsigned char* __restrict__ img1,
                                                           const unsigned char* __restrict__ img2,
                                                           const unsigned char* __restrict__ mask, long long HW,
@@ -74,7 +68,7 @@ __global__ void __launch_bounds__(256) istd_errors_kernel(const unsigned char* _
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < ISTD_SUMS; ++k) {
-    const double v = wave_sum_d(s[k]);
+    const double v = wave_sum(s[k]);
     if (lane == 0) red[k][wave] = v;
   }
   __syncthreads();
@@ -130,7 +124,7 @@ __global__ void __launch_bounds__(256) istd_ssim_kernel(const unsigned char* __r
       acc += (A1 * A2) / (B1 * B2);
     }
   }
-  acc = wave_sum_d(acc);
+  acc = wave_sum(acc);
   __shared__ double red[4];
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
@@ -212,7 +206,7 @@ __global__ void __launch_bounds__(256) istd_errors_typed_kernel(const void* __re
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < ISTD_SUMS; ++k) {
-    const double v = wave_sum_d(s[k]);
+    const double v = wave_sum(s[k]);
     if (lane == 0) red[k][wave] = v;
   }
   __syncthreads();
@@ -250,7 +244,7 @@ __global__ void __launch_bounds__(256) istd_ssim_typed_kernel(const void* __rest
       acc += (A1 * A2) / (B1 * B2);
     }
   }
-  acc = wave_sum_d(acc);
+  acc = wave_sum(acc);
   __shared__ double red[4];
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();

@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "vec16.hpp"
 
 namespace stc {
 
@@ -37,11 +38,6 @@ __global__ void pack3_kernel(const Pack3Args a) {
 }
 
 // ------------------------------------------------------------------ max-pool 2x2 s2
-__device__ __forceinline__ void unpack8(uint4 u, float* f) {
-  const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) { f[2 * q] = __uint_as_float(w[q] << 16); f[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u); }
-}
 __device__ __forceinline__ const uint4* vec_at(const View& v, int b, int y, int x, int c) {
   return reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(v.p) + vidx(v, b, y, x, c));
 }
@@ -60,7 +56,7 @@ __global__ void pool2_kernel(int B, int OH, int OW, int C8, View x, View y, View
     const int oy = (int)(r % OH), b = (int)(r / OH);
     float v[4][8];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) unpack8(*vec_at(x, b, 2 * oy + (k >> 1), 2 * ox + (k & 1), c), v[k]);
+    for (int k = 0; k < 4; ++k) Vec16<bf16>::unpack(*vec_at(x, b, 2 * oy + (k >> 1), 2 * ox + (k & 1), c), v[k]);
     float m[8];
     int am[8];
 #pragma unroll
@@ -77,7 +73,7 @@ __global__ void pool2_kernel(int B, int OH, int OW, int C8, View x, View y, View
                                                                 pack_bf16x2(m[4], m[5]), pack_bf16x2(m[6], m[7]));
     } else {
       float gv[8];
-      unpack8(*vec_at(g, b, oy, ox, c), gv);
+      Vec16<bf16>::unpack(*vec_at(g, b, oy, ox, c), gv);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         float o[8];
@@ -120,7 +116,7 @@ __global__ void vgg_norm_bwd_kernel(int B, int H, int W, View g, float* dst) {
     const long long r = i / W;
     const int y = (int)(r % H), b = (int)(r / H);
     float gv[8];
-    unpack8(*vec_at(g, b, y, x, 0), gv);
+    Vec16<bf16>::unpack(*vec_at(g, b, y, x, 0), gv);
     float* d = dst + ((long long)b * 3 * H + y) * W + x;
     const long long plane = (long long)H * W;
     d[0] = gv[0] * k0;
@@ -142,8 +138,8 @@ __global__ void feat_mse_partial_kernel(const uint4* fp, const uint4* ft, long l
     const long long i = (long long)blockIdx.x * 512 + k * 256 + threadIdx.x;
     if (i < nvec) {
       float a[8], b[8];
-      unpack8(fp[i], a);
-      unpack8(ft[i], b);
+      Vec16<bf16>::unpack(fp[i], a);
+      Vec16<bf16>::unpack(ft[i], b);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float d = a[e] - b[e];
@@ -180,8 +176,8 @@ __global__ void feat_mse_bwd_kernel(const uint4* fp, const uint4* ft, long long 
   const double s = (double)gout[0] * 2.0;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long long)gridDim.x * blockDim.x) {
     float a[8], b[8], o[8];
-    unpack8(fp[i], a);
-    unpack8(ft[i], b);
+    Vec16<bf16>::unpack(fp[i], a);
+    Vec16<bf16>::unpack(ft[i], b);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       o[e] = (float)(s * ((double)a[e] - (double)b[e]) / (double)n);

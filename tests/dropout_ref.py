@@ -341,7 +341,7 @@ for _l, _c in _LAYOUT_CROP.items():
                   BwdCase(_l, _c, 0.75, 0.0, "lo", 1.0, g1="hi"),
                   BwdCase(_l, _c, 0.6, 0.5, "dense", 0.0)]
 BWD_CASES += [BwdCase("cg1", "pixel", 0.5, 0.0, "dense", 1.0)]
-BIG_P = 65537  # more than 256 chunks: bn_bwd_finalize_kernel behind the drop reduce
+BIG_P = 65537  # more than 256 chunks: bn_bwd_finalize_kernel<BlockMerge> behind the drop reduce
 BWD_CASES += [BwdCase("cg3", "both", 0.3, 0.0, "dense", 0.2, g1="hi", kind="real"),
               BwdCase("cg64", "both", 0.3, 0.2, None, 0.0, kind="real"),
               BwdCase("cg1big", "one", 0.3, 0.0, "dense", 0.2, kind="real", shape=(1, 1, 1, BIG_P + 3, 1, BIG_P))]

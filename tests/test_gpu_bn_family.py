@@ -249,9 +249,9 @@ FINALIZE_NCH = [1, 2, 64, 65, 256, 257, 512, 513, 1024, 1025, 2048, 2049, 4096, 
 @pytest.mark.parametrize("C", [3, 4, 5])
 @pytest.mark.parametrize("nch", FINALIZE_NCH)
 def test_finalize_synthetic_partials(nch, C):
-    """bn_finalize_wave_kernel (nch <= 256 / 512 / 1024, and its c >= C guard at C = 3, 5) and bn_finalize_kernel
-    (nch <= 2048 / 4096 and the loop above) on hand-made partials with empty chunks, a constant channel and a
-    channel of slightly negative chunk M2; running buffers, update_running=False and bn_running_update.
+    """bn_finalize_kernel<WaveMerge> (nch <= 256 / 512 / 1024, and its c >= C guard at C = 3, 5) and
+    bn_finalize_kernel<BlockMerge> (nch <= 2048 / 4096 and the loop above) on hand-made partials with empty chunks, a
+    constant channel and a channel of slightly negative chunk M2; running buffers, update_running=False and bn_running_update.
     Measured worst error / bound (MI355X): mean 0.104, rstd 0.116, scale 0.179, shift 0.220, running_mean 0.194,
     running_var 0.200 of 4 * EPS32 * sum|terms|; mean and rstd 0.50 of one fp32 ulp."""
     check_finalize(make_partials(nch, C), nch, C, f"nch={nch} C={C}")

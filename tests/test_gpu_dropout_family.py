@@ -1,4 +1,4 @@
-"""The use_dropout=True kernels of csrc/bn.hip (bn_apply_drop_kernel, bn_bwd_reduce_drop_kernel,
+"""The use_dropout=True kernels of csrc/bn.hip (bn_apply_drop_kernel, bn_bwd_reduce_kernel<T, PhiloxMask>,
 bn_bwd_apply_drop_kernel, dropout_mask_kernel, dropout_next_kernel) and the mask function of csrc/philox.hpp against
 the independent references of tests/dropout_ref.py: the numpy Philox for every keep bit, fp64 arithmetic on operands
 chosen so that a correct kernel must EQUAL the reference (apply, the reduce's partials, dgamma, dbeta), and derived
@@ -227,13 +227,13 @@ def gpu_tables(case, dt):
 
 @pytest.mark.parametrize("case,dt", case_params(R.BWD_CASES))
 def test_backward(case, dt):
-    """bn_bwd_reduce_drop_kernel and bn_bwd_apply_drop_kernel (with the backward finalize between them) through the C
-    entry points, on every thread layout (the idle lanes pl >= RL at CG = 3 and 24), cropped x and dx, g1 dense or
+    """bn_bwd_reduce_kernel<T, PhiloxMask> and bn_bwd_apply_drop_kernel (with the backward finalize between them) through
+    the C entry points, on every thread layout (the idle lanes pl >= RL at CG = 3 and 24), cropped x and dx, g1 dense or
     the upper half of a 2C-wide NaN-surrounded buffer, g2 absent / dense / a lower half.
     exact cases (p = 0.5, 0.75, 0.2, 0.6): the partials, dgamma and dbeta EQUAL the fp64 sums; with slope 0.2 the
       term g2 * fl32(0.2) cannot be summed exactly and the sums take the derived bound (dropout_ref's docstring).
     real-valued cases (p = 0.3; tables from ops.bn_train_table): within m * EPS32 * sum|terms|; P = 65537 gives 1024
-      chunks (asserted), so bn_bwd_finalize_kernel runs behind the drop reduce, with empty tail chunks.
+      chunks (asserted), so bn_bwd_finalize_kernel<BlockMerge> runs behind the drop reduce, with empty tail chunks.
     dx within 16 * EPS32 * (|k1 dn| + |k2 x| + |k0|) + |k1| * EPS32 * (2 |t1| + |t2|) of the fp64 value (bf16: inside
     the rounding interval of such a value).  The second part was added after the P = 65537 fp32 case missed the first
     alone by 7.9 x: a derivation error, not a kernel error -- a correctly rounded fp32 evaluation on the CPU misses

@@ -21,6 +21,8 @@
  *   stc_in_fwd / stc_in_bwd  InstanceNorm2d forward/backward fused with LeakyReLU/ReLU, STCGAN/networks.py:107,109,170,179 with norm_layer=nn.InstanceNorm2d
  *   stc_bn_apply_drop / stc_bn_bwd_*_drop / stc_dropout_*  nn.Dropout after the up-norm (use_dropout=True),
  *                    STCGAN/networks.py UnetSkipConnectionBlock: counter-based Philox masks, nothing stored
+ *   stc_bn_bwd_frozen / stc_bn_running_rstd  BatchNorm2d backward on running statistics (module in eval mode, or frozen
+ *                    under a train-mode network), one pass: the same reference lines with training=False
  *   stc_tanh_bias_bwd Tanh backward + outermost ConvT bias grad (networks.py:112-116)
  *   stc_gather_nchw / stc_scatter_nchw              torch.cat input concat (stcgan.py:219-227,269-272) / its backward
  *   stc_loss_fwd / stc_loss_bwd                     DataLoss (L1) and AdversarialLoss (MSE / BCE-with-logits), loss.py:14-26,59-86
@@ -375,6 +377,22 @@ int stc_bn_bwd_apply_drop(int dtype, int B, stc_view x, int C,
                           stc_view g1, float slope1, stc_view g2, float slope2, const stc_dropout* drop,
                           const float* part2, int nchunks,
                           stc_view dx, float* dgamma, float* dbeta, void* stream);
+
+/* ---- frozen statistics: a BatchNorm2d that normalises with its running statistics (module in eval mode) ----
+ * Forward: the eval table of stc_bn_finalize (part == NULL) through stc_bn_apply / stc_bn_apply_drop; the buffers
+ * are not touched.  stc_bn_running_rstd: rstd[c] = 1 / sqrt(running_var[c] + eps), the factor inside that table's
+ * scale.  stc_bn_bwd_frozen: with dn as in stc_bn_bwd_reduce (g1 times keep/(1-p) when drop != NULL, which needs g1),
+ *   dx = scale * dn,  dbeta = sum dn,  dgamma = sum dn * (x - mean) * rstd      (mean = running_mean, rstd as above)
+ * in one pass over the tensor.  dgamma / dbeta non-NULL: part holds nchunks = stc_chan_stats_chunks(B, H, W) chunks of
+ * [C][2] floats and the sums are bit-identical to stc_bn_bwd_reduce + stc_bn_bwd_apply's on the same tables.  Both
+ * NULL (no parameter gradient wanted): no sums, mean / rstd / part unused, a streaming pass where every view is
+ * pixel-dense.                                                                                              */
+int stc_bn_running_rstd(int C, const float* running_var, float eps, float* rstd, void* stream);
+int stc_bn_bwd_frozen(int dtype, int B, stc_view x, int C,
+                      const float* scale, const float* shift, const float* mean, const float* rstd,
+                      stc_view g1, float slope1, stc_view g2, float slope2, const stc_dropout* drop /* NULL: none */,
+                      float* part, int nchunks,
+                      stc_view dx, float* dgamma, float* dbeta, void* stream);
 
 /* y = tanh(q) stored NCHW fp32 (the generator output).  dq = gy*(1-y^2) into NHWC
  * view dq; dbias[c] = sum dq (deterministic).                               */

@@ -8,6 +8,7 @@
 // plus the running-stat update.  Nothing normalised is written to HBM.
 // Backward: dn = g1*act1'(n) + g2*act2'(n) is recomputed on the fly from the raw
 // input (n = x*scale + shift), reduced to sum(dn), sum(dn*xhat), then applied.
+// On running statistics (eval mode / frozen layers) dx = scale*dn needs no sum: one pass (stc_bn_bwd_frozen).
 // All reductions are fixed-order => bitwise reproducible.
 //
 // Each piece is stated once and the kernels are thin users of it, but for the reduction layout, which
@@ -15,6 +16,8 @@
 //   ChunkReduce          the per-chunk reduction skeleton (chan_sum, bn_bwd_reduce)
 //   WaveMerge/BlockMerge the two reduction policies of the chunk merges (bn_finalize, bn_bwd_finalize)
 //   NoMask/PhiloxMask    the compile-time dropout policy (bn_bwd_reduce; the *_drop element-wise kernels)
+//   bn_bwd_reduce_body   the backward's chunk reduction, with or without the dx store (bn_bwd_reduce, and
+//                        bn_bwd_frozen_sums: running statistics, where that one pass is the whole backward)
 //   bn_fwd_emit          the forward per element: n, the optional mask, one or two activations
 //   bn_bwd_table/_dx     the backward per element: the k0/k1/k2 table and dx from (v, g1, g2, mask); dn_term is
 //                        one gradient's term of dn (dn_add: of a whole vector, as the reduce adds it)
@@ -377,11 +380,13 @@ __device__ __forceinline__ void bn_bwd_dx(const GradIn& gi, const float* sc, con
 }
 
 // part2[chunk][c] = {sum dn, sum dn*xhat}.  With PhiloxMask g1 is required and no mask is stored: it is
-// recomputed from the call's counter.
-template <typename T, class M>
-__global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(View x, PixDiv pd, long long P, int C, const float* scale,
-                                                            const float* shift, const float* mean, const float* rstd,
-                                                            GradIn gi, float* part, int nchunks, M mask) {
+// recomputed from the call's counter.  DX (frozen statistics, bn_bwd_frozen_sums_kernel): the pass also stores
+// dx = scale * dn, which with fixed mean / rstd is the whole input gradient.
+template <typename T, class M, bool DX>
+__device__ __forceinline__ void bn_bwd_reduce_body(const View& x, const PixDiv& pd, long long P, int C,
+                                                   const float* scale, const float* shift, const float* mean,
+                                                   const float* rstd, const GradIn& gi, float* part, int nchunks,
+                                                   const M& mask, const View& dx) {
   constexpr int N = Vec16<T>::N;
   ChunkReduce<2 * N> r(P, C / N, nchunks);
   const int c = N * r.cg;
@@ -414,6 +419,12 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(View x, PixDiv pd, l
           Vec16<T>::load(vptr<T>(gi.g2, b, yy, xx, c), g);
           dn_add<N, false>(g, nullptr, n, gi.s2, d);
         }
+        if constexpr (DX) {
+          float o[N];
+#pragma unroll
+          for (int e = 0; e < N; ++e) o[e] = sc[e] * d[e];
+          Vec16<T>::store(reinterpret_cast<T*>(dx.p) + vidx(dx, b, yy, xx, c), o);
+        }
 #pragma unroll
         for (int e = 0; e < N; ++e) {
           acc[e] += d[e];
@@ -425,6 +436,24 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(View x, PixDiv pd, l
     for (int e = 0; e < N; ++e)
       *reinterpret_cast<float2*>(part + ((long long)blockIdx.x * C + c + e) * 2) = make_float2(acc[e], acc[N + e]);
   }
+}
+
+template <typename T, class M>
+__global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(View x, PixDiv pd, long long P, int C, const float* scale,
+                                                            const float* shift, const float* mean, const float* rstd,
+                                                            GradIn gi, float* part, int nchunks, M mask) {
+  bn_bwd_reduce_body<T, M, false>(x, pd, P, C, scale, shift, mean, rstd, gi, part, nchunks, mask, x);
+}
+
+// Frozen statistics (the layer normalised with its running statistics; scale / shift = the eval table, mean / rstd =
+// running_mean / rstd_run): the reduce above that also writes dx -- one pass where the train-mode backward takes a
+// reduce, a merge and an apply.  bn_bwd_finalize_kernel merges the partials as there.
+template <typename T, class M>
+__global__ void __launch_bounds__(256) bn_bwd_frozen_sums_kernel(View x, PixDiv pd, long long P, int C,
+                                                                 const float* scale, const float* shift,
+                                                                 const float* mean, const float* rstd, GradIn gi,
+                                                                 float* part, int nchunks, View dx, M mask) {
+  bn_bwd_reduce_body<T, M, true>(x, pd, P, C, scale, shift, mean, rstd, gi, part, nchunks, mask, dx);
 }
 
 // dbeta[c] = sum dn, dgamma[c] = sum dn*xhat  (fixed order over chunks, the policy's lanes per channel)
@@ -815,6 +844,91 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_drop_kernel(View x, PixDiv p
   }
 }
 
+// Frozen statistics, no parameter gradient wanted: dx = scale * dn alone, a plain streaming pass (no sums, no
+// partials).  DENSE: the streaming form of bn_bwd_apply_kernel (no mask: it needs (b, y, x) of every vector);
+// otherwise general addressing, with the dropout factor on g1 under PhiloxMask.
+template <typename T, bool DENSE, class M>
+__global__ void __launch_bounds__(256) bn_bwd_frozen_kernel(View x, PixDiv pd, long long P, int C, const float* scale,
+                                                            const float* shift, GradIn gi, View dx, M mask) {
+  static_assert(!(DENSE && M::ON), "the streaming form has no pixel coordinates for the mask");
+  constexpr int N = Vec16<T>::N;
+  const int CG = C / N;
+  struct In {
+    float v[N], g1[N], g2[N];
+  };
+  // dn as the reduce forms it (the same terms in the same order), then dx
+  auto dx_of = [&](const In& in, const float* sc, const float* sh, const float* m, float* d) {
+    float n[N], dn[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) { n[e] = fmaf(in.v[e], sc[e], sh[e]); dn[e] = 0.f; }
+    if (M::ON || gi.has1) dn_add<N, M::ON>(in.g1, m, n, gi.s1, dn);
+    if (gi.has2) dn_add<N, false>(in.g2, nullptr, n, gi.s2, dn);
+#pragma unroll
+    for (int e = 0; e < N; ++e) d[e] = sc[e] * dn[e];
+  };
+  if constexpr (DENSE) {  // (host: stream_ok for every view)
+    const unsigned nthr = gridDim.x * blockDim.x, t0 = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned pstep = nthr / (unsigned)CG, Pu = (unsigned)P;
+    unsigned pix = t0 / (unsigned)CG;
+    if (pix >= Pu) return;
+    const int c = N * (int)(t0 % (unsigned)CG);
+    float sc[N], sh[N];
+    ldc<N>(scale + c, sc); ldc<N>(shift + c, sh);
+    const T* xp = reinterpret_cast<const T*>(x.p) + x.co + c;
+    const T* g1p = reinterpret_cast<const T*>(gi.g1.p) + gi.g1.co + c;
+    const T* g2p = reinterpret_cast<const T*>(gi.g2.p) + gi.g2.co + c;
+    T* dp = reinterpret_cast<T*>(dx.p) + dx.co + c;
+    const unsigned xs = x.ps, g1s = gi.g1.ps, g2s = gi.g2.ps, ds = dx.ps;
+    auto ld = [&](unsigned q, In& in) {
+      Vec16<T>::load(xp + q * xs, in.v);
+      if (gi.has1) Vec16<T>::load(g1p + q * g1s, in.g1);
+      if (gi.has2) Vec16<T>::load(g2p + q * g2s, in.g2);
+    };
+    auto put = [&](unsigned q, const In& in) {
+      float d[N];
+      dx_of(in, sc, sh, nullptr, d);
+      Vec16<T>::store(dp + q * ds, d);
+    };
+    for (; pix + pstep < Pu; pix += 2 * pstep) {  // both pixels' loads in flight before either is used
+      In a, b;
+      ld(pix, a);
+      ld(pix + pstep, b);
+      put(pix, a);
+      put(pix + pstep, b);
+    }
+    if (pix < Pu) {
+      In a;
+      ld(pix, a);
+      put(pix, a);
+    }
+  } else {
+    const long long total = P * CG;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const typename M::Key key = mask.key();
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
+      const int c = N * (int)(idx % CG);
+      int b, yy, xx;
+      pix_bxy(pd, idx / CG, b, yy, xx);
+      In in;
+      float sc[N], sh[N], m[N], d[N];
+      Vec16<T>::load(vptr<T>(x, b, yy, xx, c), in.v);
+      if (M::ON || gi.has1) Vec16<T>::load(vptr<T>(gi.g1, b, yy, xx, c), in.g1);
+      if (gi.has2) Vec16<T>::load(vptr<T>(gi.g2, b, yy, xx, c), in.g2);
+      ldc<N>(scale + c, sc); ldc<N>(shift + c, sh);
+      if constexpr (M::ON) mask.template factor<N>(key, mask.index(C, b, yy, xx, c), m);
+      dx_of(in, sc, sh, m, d);
+      Vec16<T>::store(reinterpret_cast<T*>(dx.p) + vidx(dx, b, yy, xx, c), d);
+    }
+  }
+}
+
+// rstd_run = 1 / sqrt(running_var + eps), as bn_eval_table_kernel forms it inside scale
+__global__ void bn_running_rstd_kernel(int C, const float* rvar, float eps, float* rstd) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  rstd[c] = 1.f / sqrtf(rvar[c] + eps);
+}
+
 // keep (1) / drop (0) of every element of the full extent [B][H][W][C], 4 channels (one Philox call) per thread
 __global__ void __launch_bounds__(256) dropout_mask_kernel(DropDev drop, long long quads, unsigned char* out) {
   const DropKey k = drop_key(drop);
@@ -1096,6 +1210,60 @@ extern "C" int stc_bn_bwd_apply_drop(int dtype, int B, stc_view x, int C, const 
   const Pixels s = pixels_of(dtype, B, x, C);
   View o = mkview(dx);
   STC_DT(dtype, hipLaunchKernelGGL(bn_bwd_apply_drop_kernel<T_>, dim3(grid_for(s.work)), dim3(256), 0, st, s.v, s.pd, s.P, C, scale, shift, mean, rstd, gamma, gi, dgamma, dbeta, o, mask));
+  STC_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- frozen statistics (a BatchNorm layer that normalises with its running statistics)
+extern "C" int stc_bn_running_rstd(int C, const float* running_var, float eps, float* rstd, void* stream) {
+  STC_REQUIRE(C > 0 && running_var && rstd, "stc_bn_running_rstd: running_var and an output of C > 0 floats required");
+  hipLaunchKernelGGL(bn_running_rstd_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, C, running_var,
+                     eps, rstd);
+  STC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stc_bn_bwd_frozen(int dtype, int B, stc_view x, int C, const float* scale, const float* shift,
+                                 const float* mean, const float* rstd, stc_view g1, float slope1, stc_view g2,
+                                 float slope2, const stc_dropout* drop, float* part, int nchunks, stc_view dx,
+                                 float* dgamma, float* dbeta, void* stream) {
+  STC_REQUIRE(vec_ok(dtype, C, x) && dx.p && vec_ok(dtype, C, dx) && (!g1.p || vec_ok(dtype, C, g1)) &&
+                  (!g2.p || vec_ok(dtype, C, g2)),
+              "stc_bn_bwd_frozen: bad C=%d / views", C);
+  STC_REQUIRE(scale && shift, "stc_bn_bwd_frozen: the scale / shift table is required");
+  STC_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), "stc_bn_bwd_frozen: dgamma / dbeta must come together");
+  const bool sums = dgamma != nullptr;
+  const Pixels s = pixels_of(dtype, B, x, C);
+  if (sums) {
+    STC_REQUIRE(mean && rstd && part, "stc_bn_bwd_frozen: running mean / rstd tables and a partials buffer required");
+    STC_REQUIRE(nchunks == stat_chunks(s.P), "stc_bn_bwd_frozen: nchunks=%d, not the %d chunks of %lld pixels",
+                nchunks, stat_chunks(s.P), s.P);
+  }
+  PhiloxMask mask;
+  if (drop) {
+    STC_REQUIRE(g1.p, "stc_bn_bwd_frozen: a dropout block needs g1, the gradient that passes through it");
+    if (int rc = mkdrop(drop, B, C, &mask.d, "stc_bn_bwd_frozen")) return rc;
+    STC_REQUIRE(x.H <= drop->H && x.W <= drop->W, "stc_bn_bwd_frozen: view outside the dropout extent");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  GradIn gi = mkgrad(g1, slope1, g2, slope2);
+  View o = mkview(dx);
+  if (sums) {
+    if (drop) STC_DT(dtype, hipLaunchKernelGGL((bn_bwd_frozen_sums_kernel<T_, PhiloxMask>), dim3(nchunks), dim3(256), 0, st, s.v, s.pd, s.P, C, scale, shift, mean, rstd, gi, part, nchunks, o, mask));
+    else STC_DT(dtype, hipLaunchKernelGGL((bn_bwd_frozen_sums_kernel<T_, NoMask>), dim3(nchunks), dim3(256), 0, st, s.v, s.pd, s.P, C, scale, shift, mean, rstd, gi, part, nchunks, o, NoMask{}));
+    STC_CHECK_LAUNCH();
+    bwd_finalize(part, nchunks, C, dgamma, dbeta, st);
+    STC_CHECK_LAUNCH();
+    return 0;
+  }
+  const int N = dtype == STC_F32 ? 4 : 8;
+  const bool dense = !drop && stream_ok(B, x, C, N) && stream_ok(B, dx, C, N) && stream_ok(B, g1, C, N) && stream_ok(B, g2, C, N);
+  const int blocks = dense ? grid_stream(s.work) : grid_for(s.work);
+#define STC_FZ(D_, M_, m_) STC_DT(dtype, hipLaunchKernelGGL((bn_bwd_frozen_kernel<T_, D_, M_>), dim3(blocks), dim3(256), 0, st, s.v, s.pd, s.P, C, scale, shift, gi, o, m_))
+  if (dense) STC_FZ(true, NoMask, NoMask{});
+  else if (drop) STC_FZ(false, PhiloxMask, mask);
+  else STC_FZ(false, NoMask, NoMask{});
+#undef STC_FZ
   STC_CHECK_LAUNCH();
   return 0;
 }

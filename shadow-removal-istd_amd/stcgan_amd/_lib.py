@@ -119,6 +119,9 @@ _SIGS = {
                                       _i32, _vp]),
     "stc_bn_bwd_apply_drop": (_i32, [_i32, _i32, View, _i32, _vp, _vp, _vp, _vp, _vp, View, _f32, View, _f32, _vp, _vp,
                                      _i32, View, _vp, _vp, _vp]),
+    "stc_bn_running_rstd": (_i32, [_i32, _vp, _f32, _vp, _vp]),
+    "stc_bn_bwd_frozen": (_i32, [_i32, _i32, View, _i32, _vp, _vp, _vp, _vp, View, _f32, View, _f32, _vp, _vp, _i32,
+                                 View, _vp, _vp, _vp]),
     "stc_tanh_bias_bwd": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, View, _vp, _vp, _i32, _vp]),
     "stc_gather_nchw": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, View, _i32, _vp]),
     "stc_scatter_nchw": (_i32, [_i32, _i32, _i32, _i32, View, _i32, _vp, _vp, _vp]),

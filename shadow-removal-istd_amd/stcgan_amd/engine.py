@@ -27,6 +27,10 @@ norm_layer=nn.InstanceNorm2d (GenPlan.inorm / DiscPlan.inorm; DESIGN.md section 
 "BN" above an instance norm -- a normed layer is the plain conv, then one ops.in_forward (statistics per sample over
 the stored raw output + the activation pass); its backward the input-gradient conv, then one ops.in_backward.  The
 BatchNorm path takes none of these calls.
+
+BatchNorm layers on their running statistics (eval mode, or norm children frozen under a train-mode network;
+DESIGN.md section 8e): conv, the eval table (+ rstd_run when a backward follows) and ops.bn_apply forward; backward the
+input-gradient conv, then one ops.bn_backward_frozen (one pass; the sums only where parameter gradients are wanted).
 """
 import torch
 
@@ -287,9 +291,10 @@ def _conv_in_act(kind, B, xv, cin, w, cout, yv, dt, norm, apply_x, y1, s1, y2=No
     return ops.in_forward(B, yv, cout, dt, norm, apply_x, y1, s1, y2, s2)
 
 
-def _conv_bn(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev):
+def _conv_bn(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev, keep=False):
     """Conv whose output feeds a BatchNorm2d: returns ((2, cout) scale/shift table, (mean, rstd) or None).
-    Train mode: the batch statistics come out of the conv itself (stc_conv_fwd_ex)."""
+    Train mode (batch statistics): they come out of the conv itself (stc_conv_fwd_ex).  Otherwise the table is built
+    from the running statistics; ``keep`` (a backward will follow): (running_mean, rstd_run) beside it."""
     t = torch.empty((2, cout), dtype=torch.float32, device=dev)
     if train:
         part, nch = ops.conv_stats(kind, B, xv, cin, w, cout, yv, dt)
@@ -297,29 +302,34 @@ def _conv_bn(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev):
     else:
         ops.conv(kind, B, xv, cin, w, cout, yv, dt)
         ops.bn_eval_table(cout, bn, t[0], t[1])
-        st = None
+        st = (bn.running_mean, ops.bn_running_rstd(cout, bn)) if keep else None
     return t, st
 
 
 def _conv_bn_act(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev, apply_x, y1, s1, y2=None, s2=0.0, defer=None,
-                 drop=None):
+                 drop=None, keep=False):
     """Conv -> BatchNorm2d -> activation pass of ``apply_x`` into y1 [and y2] (y1 None: none); returns _conv_bn's
-    (table, (mean, rstd) or None).  Train mode: one library call (ops.conv_bn_act); ``defer`` (a list): the running
-    statistics are not updated, the update's inputs are appended (ops.bn_running_update); ``drop`` (train mode
-    only): a dropout level between the BatchNorm and the activation (ops.dropout_next)."""
+    (table, (mean, rstd) or None).  ``train``: the layer uses batch statistics -- one library call
+    (ops.conv_bn_act); ``defer`` (a list): the running statistics are not updated, the update's inputs are appended
+    (ops.bn_running_update).  Otherwise (running statistics: eval mode, or frozen norm layers) conv, table and
+    ops.bn_apply, ``defer`` ignored and ``keep`` as in _conv_bn.  ``drop``: a dropout level between the BatchNorm and
+    the activation (ops.dropout_next), in either form."""
     if train:
         return ops.conv_bn_act(kind, B, xv, cin, w, cout, yv, dt, bn, apply_x, y1, s1, y2, s2, defer=defer, drop=drop)
-    assert drop is None, "dropout is the identity in eval mode"
-    t, st = _conv_bn(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev)
+    t, st = _conv_bn(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev, keep=keep)
     if y1 is not None:
-        ops.bn_apply(B, apply_x, cout, dt, (t[0], t[1]), y1, s1, y2, s2)
+        ops.bn_apply(B, apply_x, cout, dt, (t[0], t[1]), y1, s1, y2, s2, drop=drop)
     return t, st
 
 
 # ----------------------------------------------------------------------------- generator
 
 
-def gen_forward(plan, sources, train, dt, cache, save):
+def gen_forward(plan, sources, train, dt, cache, save, batch_stats=None):
+    """train: dropout levels active (the network's own mode).  batch_stats (None: as train): the BatchNorm layers
+    use batch statistics and update their running ones; False: running statistics, buffers untouched (frozen)."""
+    if batch_stats is None:
+        batch_stats = train
     dev = sources[0].device
     B, _, H, W = sources[0].shape
     Lv, co = plan.L, plan.co
@@ -345,7 +355,8 @@ def gen_forward(plan, sources, train, dt, cache, save):
 
     def conv_bn_act(kind, xv, cin_, w, cout, yv, bn, apply_x, y1, s1, y2=None, s2=0.0, drop=None):
         """conv -> BatchNorm (batch statistics fused into the conv in train mode) -> activation pass."""
-        return _conv_bn_act(kind, B, xv, cin_, w, cout, yv, dt, bn, train, dev, apply_x, y1, s1, y2, s2, drop=drop)
+        return _conv_bn_act(kind, B, xv, cin_, w, cout, yv, dt, bn, batch_stats, dev, apply_x, y1, s1, y2, s2,
+                            drop=drop, keep=save)
 
     # use_dropout, train mode: this call's {seed, offset} copy (one tiny launch; the generator's offset advances),
     # read from device memory by every dropout kernel of the call, forward and backward
@@ -401,7 +412,8 @@ def gen_forward(plan, sources, train, dt, cache, save):
     saved = None
     if save:
         saved = dict(S=S, xin=xin, rd=rd, ad=ad, cr=cr, rq=rq, tab_d=tab_d, tab_u=tab_u, st_d=st_d, st_u=st_u,
-                     y=y, cin=cin, cin_pad=cin_pad, src_c=[s.shape[1] for s in sources])
+                     y=y, cin=cin, cin_pad=cin_pad, src_c=[s.shape[1] for s in sources],
+                     frozen=not (plan.inorm or batch_stats))
         if drop_state is not None:
             saved["drop"] = {k: drop_of(k) for k in plan.drop}
         if TRACE is not None:
@@ -422,6 +434,7 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
     need_w = W is not None
     lane = _WgradLane() if need_w else None
     drops = saved.get("drop") or {}  # {level: dropout level of the forward call} (use_dropout, train mode)
+    frozen = saved["frozen"]  # the BatchNorm layers normalised with their running statistics
 
     def dest(p):
         return W.dest(p) if need_w else None
@@ -483,6 +496,19 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
         mean, rstd = st_u[k + 1]
         t = tab_u[k + 1]
         drop = drops.get(k + 1)
+        if frozen:
+            # running statistics: the unfused form -- the conv writes gcat[k], then the one-pass backward (dx needs
+            # no batch sum; the sums only where parameter gradients are wanted), through the dropout where there is one
+            ops.conv(L.CONV_S2, B, dqv, cg, wd, cin_t, L.nhwc_view(gcat[k], 0, *S[k + 1]), dt)
+            if need_w:
+                W.done([plan.convT[k].weight], lane)
+            ops.bn_backward_frozen(B, L.nhwc_view(rq[k + 1]), C, dt, L.nhwc_view(dq), g1=L.nhwc_view(gcat[k], C),
+                                   s1=0.0, state=(t[0], t[1], mean, rstd), dgamma=dest(bn.weight),
+                                   dbeta=dest(bn.bias), want_params=need_w, drop=drop)
+            if need_w:
+                W.done([bn.weight, bn.bias])
+            _trace("G", ("dq", k + 1), dq)
+            continue
         if drop is not None:
             # a dropout level: the gradient reaches BN_up[k+1]'s output through the mask, g * [n > 0] * keep/(1-p).
             # The unfused form -- the conv writes gcat[k], then the dropout-aware BN backward recomputes the mask
@@ -566,6 +592,18 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
                             dbeta=dest_opt(bn.bias))
             if need_w and plan.affine:
                 W.done([bn.weight, bn.bias])
+        elif frozen:  # the conv writes ga, then the one-pass ReLU / LeakyReLU + frozen-BatchNorm backward
+            mean, rstd = st_d[k - 1]
+            t = tab_d[k - 1]
+            bn = plan.bnd[k - 1]
+            ops.conv(L.CONVT_S2, B, drv, co[k], wd, cprev, L.nhwc_view(ga), dt)
+            if need_w:
+                W.done([plan.conv[k].weight], lane)
+            ops.bn_backward_frozen(B, xv, cprev, dt, L.nhwc_view(dr), g1=g1, s1=0.0, g2=L.nhwc_view(ga, 0, *S[k]),
+                                   s2=LRELU, state=(t[0], t[1], mean, rstd), dgamma=dest(bn.weight),
+                                   dbeta=dest(bn.bias), want_params=need_w)
+            if need_w:
+                W.done([bn.weight, bn.bias])
         else:  # BN reduction fused into the input-gradient conv that produces ga
             mean, rstd = st_d[k - 1]
             t = tab_d[k - 1]
@@ -606,8 +644,10 @@ def _conv_out(h, s):
     return (h + 2 - 4) // s + 1
 
 
-def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=False, defer=None):
-    """raw[i] = conv_{i-1} raw output (raw[0] = padded input); act[i] = input of conv_i.
+def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=False, defer=None,
+                 batch_stats=None):
+    """train / batch_stats: as gen_forward's (a discriminator has no dropout: only batch_stats matters).
+    raw[i] = conv_{i-1} raw output (raw[0] = padded input); act[i] = input of conv_i.
     inputs: optional dict reusing the gathered NHWC input across calls on the same source tensors
     (the trainer's real/fake pairs are fed to each discriminator twice per step, STCGAN/stcgan.py:215-280;
     valid while those tensors are alive and unmodified -- one train step)."""
@@ -616,9 +656,12 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
     cin = sum(s.shape[1] for s in sources)
     assert cin == plan.in_c, f"discriminator expects {plan.in_c} input channels, got {cin}"
     n = plan.n
+    if batch_stats is None:
+        batch_stats = train
+    if stats_only and (plan.inorm or not batch_stats):
+        # no running statistics to advance: nothing to do (the zero-element placeholder, as below)
+        return torch.empty((B, plan.convs[-1].out_channels, 0, 0), dtype=torch.float32, device=dev), None
     if plan.inorm:
-        if stats_only:  # no running statistics to advance: nothing to do (the zero-element placeholder, as below)
-            return torch.empty((B, plan.convs[-1].out_channels, 0, 0), dtype=torch.float32, device=dev), None
         hw = (H, W)
         for i, cv in enumerate(plan.convs[:-1]):
             hw = (_conv_out(hw[0], plan.strides[i]), _conv_out(hw[1], plan.strides[i]))
@@ -670,8 +713,9 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
             o = _nhwc(B, h, w, cout, dt, dev)
             ov = L.nhwc_view(o)
             # (stats_only: only the logits layer reads the last activation -- no pass)
-            t, st = _conv_bn_act(kind, B, L.nhwc_view(act[i]), chans[i], wp, cout, ov, dt, plan.bns[i - 1], train,
-                                 dev, ov, None if (stats_only and i == n - 2) else L.nhwc_view(a), LRELU, defer=defer)
+            t, st = _conv_bn_act(kind, B, L.nhwc_view(act[i]), chans[i], wp, cout, ov, dt, plan.bns[i - 1],
+                                 batch_stats, dev, ov, None if (stats_only and i == n - 2) else L.nhwc_view(a), LRELU,
+                                 defer=defer, keep=save)
             tab = (t[0], t[1])
         elif ops.conv_act(kind, B, L.nhwc_view(act[i]), chans[i], wp, cout, L.nhwc_view(a), LRELU, dt, bias=cv.bias):
             o = a  # no raw output: the backward's LeakyReLU test sees the same signs in the activation
@@ -688,7 +732,7 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
     saved = None
     if save:
         saved = dict(raw=raw, act=act, dims=dims, chans=chans, tabs=tabs, stats=stats, cin=cin, cin_pad=cin_pad,
-                     bias_ch=bias_ch,
+                     bias_ch=bias_ch, frozen=not (plan.inorm or batch_stats),
                      src_c=[s.shape[1] for s in sources])
         if TRACE is not None:
             _trace_new("D")
@@ -783,6 +827,18 @@ def disc_backward(plan, saved, gout, dt, cache, need_src, W):
                 ops.bn_backward(B, xv, cin, dt, L.nhwc_view(gn), g1=L.nhwc_view(ga), s1=LRELU)
             if need_w:
                 W.done(own, lane)
+        elif saved["frozen"]:  # the conv writes ga, then the one-pass LeakyReLU + frozen-BatchNorm backward
+            mean, rstd = stats[i]
+            bn = plan.bns[i - 2]
+            ops.conv(dkind, B, gv, gch, wd, cin, L.nhwc_view(ga), dt)
+            if need_w:
+                W.done(own, lane)
+            ops.bn_backward_frozen(B, xv, cin, dt, L.nhwc_view(gn), g1=L.nhwc_view(ga), s1=LRELU,
+                                   state=(tabs[i][0], tabs[i][1], mean, rstd),
+                                   dgamma=W.dest(bn.weight) if need_w else None,
+                                   dbeta=W.dest(bn.bias) if need_w else None, want_params=need_w)
+            if need_w:
+                W.done([bn.weight, bn.bias])
         else:
             mean, rstd = stats[i]
             bn = plan.bns[i - 2]
@@ -804,7 +860,10 @@ def disc_backward(plan, saved, gout, dt, cache, need_src, W):
 
 
 class NetFn(torch.autograd.Function):
-    """One autograd node per network call.  inputs: (ctrl, *sources, *params).
+    """One autograd node per network call.  inputs: (ctrl, *sources, *params); ctrl = (plan, kind, drop_on, dtype,
+    pack cache, sources, input cache, gradient consumer, stats_only, defer_running, batch_stats): drop_on = the
+    network's own training flag (dropout levels), batch_stats = its BatchNorm modules' (batch statistics and running
+    update, or running statistics; networks._HipNet._batch_stats).
 
     The backward returns gradients for the sources only: the parameters' gradients are written by the
     kernels straight into the network's flat gradient buffer (GradWriter), so autograd never allocates,
@@ -812,22 +871,24 @@ class NetFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ctrl, *tensors):
-        plan, kind, train, dt, cache, nsrc, inputs, _, stats_only, defer = ctrl
+        plan, kind, train, dt, cache, nsrc, inputs, _, stats_only, defer, batch_stats = ctrl
         sources = [t.contiguous().float() for t in tensors[:nsrc]]
-        save = train and any(ctx.needs_input_grad[1:])
+        save = any(ctx.needs_input_grad[1:])  # (every mode: nothing under torch.no_grad())
         ops.refresh_packs(cache)  # all operands packed since the last optimiser step, one launch
-        out, saved = (gen_forward(plan, sources, train, dt, cache, save) if kind == "G" else
-                      disc_forward(plan, sources, train, dt, cache, save, inputs, stats_only and not save, defer))
+        out, saved = (gen_forward(plan, sources, train, dt, cache, save, batch_stats) if kind == "G" else
+                      disc_forward(plan, sources, train, dt, cache, save, inputs, stats_only and not save, defer,
+                                   batch_stats))
         ctx.ctrl = ctrl
         ctx.saved_net = saved
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        plan, kind, train, dt, cache, nsrc, _, consumer, _, _ = ctx.ctrl
+        plan, kind, train, dt, cache, nsrc, _, consumer = ctx.ctrl[:8]
         saved = ctx.saved_net
         if saved is None:
-            raise RuntimeError("stcgan_amd: backward through a network called in eval mode is not supported")
+            raise RuntimeError("stcgan_amd: this network call saved nothing for a backward (a second backward "
+                               "through the same call?)")
         need = ctx.needs_input_grad[1:]
         need_src = list(need[:nsrc]) if any(need[:nsrc]) else None  # per source, or None
         W = GradWriter(plan.net) if any(need[nsrc:]) else None

@@ -16,6 +16,11 @@ generator of its own, ``set_dropout_seed`` / ``dropout_state``, not torch's); od
 src/models/stcgan_g.py:120-132 (the STCGAN/networks.py version raises there);
 forward also accepts a list/tuple of NCHW tensors, treated as their channel
 concatenation without materialising it (what ``torch.cat(..., 1)`` would give).
+
+Modes are torch's, read from the modules at every call: the network's own ``training`` flag governs the dropout
+levels, its BatchNorm2d children's flags govern batch statistics + running update (train) against running statistics
+with untouched buffers (eval) -- ``net.eval()``, or ``net.train()`` with the norm children in eval (``freeze_norm``).
+Every mode has a backward.  BatchNorm children in mixed modes raise NotImplementedError.
 """
 import torch
 import torch.nn as nn
@@ -88,6 +93,7 @@ class _HipNet(nn.Module):
         self.compute_dtype = torch.float32
         self._pack_cache = {}
         self._plan = None
+        self._bn_named = None  # [(name, BatchNorm2d child)], made at the first call (_batch_stats)
         # parallel.BucketExchange averaging this network's gradients over the ranks while its backward runs
         # (set by the trainer when world > 1), or None
         self.grad_exchange = None
@@ -116,6 +122,7 @@ class _HipNet(nn.Module):
 
     def _run(self, inp):
         sources = list(inp) if isinstance(inp, (list, tuple)) else [inp]
+        batch_stats = self._batch_stats()  # (first: mixed BatchNorm modes are refused whatever the inputs)
         for s in sources:
             if not s.is_cuda:
                 raise RuntimeError("stcgan_amd networks run on the GPU only (HIP kernels); move the model and "
@@ -124,8 +131,34 @@ class _HipNet(nn.Module):
             self._plan = self._make_plan()
         params = self._plan.params
         ctrl = (self._plan, self.kind, self.training, self.compute_dtype, self._pack_cache, len(sources),
-                self.input_cache, self.grad_consumer, self.stats_only, self.defer_running)
+                self.input_cache, self.grad_consumer, self.stats_only, self.defer_running, batch_stats)
         return engine.NetFn.apply(ctrl, *sources, *params)
+
+    def _batch_stats(self):
+        """Whether this call's BatchNorm layers use batch statistics (and update their running ones): their own
+        ``training`` flags, all alike.  Instance norm has one mode: the network's flag, which nothing reads."""
+        named = self._bn_named
+        if named is None:  # (the module tree is fixed at construction)
+            named = self._bn_named = [(n, m) for n, m in self.named_modules() if isinstance(m, nn.BatchNorm2d)]
+        on = sum(m.training for _, m in named)
+        if on == len(named):
+            return bool(named) or self.training
+        if on == 0:
+            return False
+        raise NotImplementedError(
+            "stcgan_amd: BatchNorm2d layers of one network in mixed modes are not supported -- in train mode: "
+            + ", ".join(n for n, m in named if m.training) + "; in eval mode: "
+            + ", ".join(n for n, m in named if not m.training) + " (freeze_norm() switches all of them)")
+
+    def freeze_norm(self, on=True):
+        """Put exactly the norm children in eval mode (BatchNorm2d: running statistics, buffers untouched; the
+        usual fine-tuning idiom), or with ``on=False`` back into the network's own mode.  Dropout keeps following
+        the network's mode.  ``net.train()`` / ``net.eval()`` reset every child, as in torch: call this after
+        them.  No effect on the computation of instance-norm networks.  Returns self."""
+        for m in self.modules():
+            if isinstance(m, (nn.BatchNorm2d, nn.InstanceNorm2d)):
+                m.training = self.training and not on
+        return self
 
     def _apply(self, fn, *args, **kwargs):
         self._pack_cache.clear()

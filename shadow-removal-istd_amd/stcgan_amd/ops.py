@@ -783,6 +783,41 @@ def bn_backward(B, xv, C, dt, dxv, g1=None, s1=0.0, g2=None, s2=0.0, bn_state=No
     return dgamma, dbeta
 
 
+def bn_running_rstd(C, bn, out=None):
+    """rstd_run[c] = 1 / sqrt(running_var[c] + eps) of a BatchNorm2d (stc_bn_running_rstd): the factor inside
+    bn_eval_table's scale, which the frozen-statistics backward needs on its own for dgamma."""
+    out = _out1(out, C, bn.running_var.device)
+    check(lib().stc_bn_running_rstd(C, ptr(bn.running_var), float(bn.eps), ptr(out), stream()), "stc_bn_running_rstd")
+    return out
+
+
+def bn_backward_frozen(B, xv, C, dt, dxv, g1, s1, g2=None, s2=0.0, state=None, dgamma=None, dbeta=None,
+                       want_params=True, drop=None):
+    """Fused activation + BatchNorm backward of a layer that normalised with its running statistics
+    (stc_bn_bwd_frozen; one pass): dx = scale * dn into dxv, with dn as in bn_backward.  state = (scale, shift,
+    running_mean, rstd_run) -- bn_eval_table's table, the buffer itself and bn_running_rstd.  want_params: also
+    dbeta = sum dn and dgamma = sum dn * xhat (written into ``dgamma`` / ``dbeta`` when given); returns them, or
+    (None, None) -- then no sums are formed and no partials buffer exists.  drop (a dropout level, see dropout_next;
+    needs g1): g1 reaches the BatchNorm output through the dropout, as in bn_backward."""
+    scale, shift, mean, rstd = state
+    dev = scale.device
+    d = _drop(drop) if drop is not None else None
+    part, nch = None, 0
+    if want_params:
+        nch = stats_chunks(B, xv.H, xv.W)
+        part = torch.empty((nch, C, 2), dtype=torch.float32, device=dev)
+        dgamma = _out1(dgamma, C, dev)
+        dbeta = _out1(dbeta, C, dev)
+    else:
+        dgamma = dbeta = None
+    check(lib().stc_bn_bwd_frozen(L.dtype_code(dt), B, xv, C, ptr(scale), ptr(shift), ptr(mean), ptr(rstd),
+                                  g1 if g1 is not None else L.NULL_VIEW, float(s1),
+                                  g2 if g2 is not None else L.NULL_VIEW, float(s2),
+                                  ctypes.byref(d) if d is not None else None, ptr(part), nch, dxv, ptr(dgamma),
+                                  ptr(dbeta), stream()), "stc_bn_bwd_frozen")
+    return dgamma, dbeta
+
+
 def in_plan(B, H, W, C, dt):
     """(regime 0 tiny / 1 resident / 2 streamed, channels per slab, pixel chunks per sample, m) of stc_in_plan."""
     key = ("inp", B, H, W, C, dt)

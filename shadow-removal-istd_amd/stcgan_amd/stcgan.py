@@ -145,6 +145,13 @@ LATE_STATS_CALLS = True
 # the reference does
 EARLY_D_BACKWARD = 2
 
+def check_freeze_norm(v):
+    """args.freeze_norm as a bool (True / False / 0 / 1; ValueError otherwise)."""
+    if not isinstance(v, (bool, int)) or v not in (0, 1):
+        raise ValueError(f"stcgan_amd: args.freeze_norm must be a bool, got {v!r}")
+    return bool(v)
+
+
 class STCGAN(object):
 
     def __init__(self, args, train_loader=None, valid_loader=None):
@@ -162,6 +169,10 @@ class STCGAN(object):
         if self.norm not in ("batch", "instance"):
             raise ValueError(f"stcgan_amd: args.norm must be 'batch' or 'instance', got {self.norm!r}")
         nl = dict(norm_layer=torch.nn.InstanceNorm2d if self.norm == "instance" else torch.nn.BatchNorm2d)
+        # args.freeze_norm (False): train steps run with the BatchNorm layers of all four networks on their running
+        # statistics, which then never move (fine-tuning a checkpoint on few images or at batch size 1-2); dropout,
+        # where configured, stays active.  No effect with args.norm = "instance".
+        self.freeze_norm = check_freeze_norm(getattr(args, "freeze_norm", False))
         # args.optimizer: "adam" (default) or "adamw"; args.weight_decay (0) and args.amsgrad (False) go to both
         # optimisers -- coupled L2 decay with "adam", decoupled with "adamw" (optim.Adam / optim.AdamW)
         self.optimizer = getattr(args, "optimizer", "adam")
@@ -189,6 +200,7 @@ class STCGAN(object):
         for net in (self.G1, self.G2, self.D1, self.D2):
             net.to(self.device)
             net.set_compute_dtype(dtype)
+        self._apply_freeze()
         # every rank starts from rank 0's weights (DataParallel replicates dev0's module)
         parallel.broadcast_state([self.G1, self.G2, self.D1, self.D2])
         if self.use_dropout:
@@ -402,11 +414,21 @@ class STCGAN(object):
                 gout = torch.full((), weight, dtype=torch.float32, device=self.device)
             torch.autograd.backward(C, d_term_grad(self.adv_loss, C, lam, gout, real))
 
+    def _apply_freeze(self):
+        """args.freeze_norm: the norm layers of every network that is in train mode go (back) to eval -- after
+        construction and after every ``.train()``, which resets the children."""
+        if self.freeze_norm:
+            for net in (self.G1, self.G2, self.D1, self.D2):
+                if net.training:
+                    net.freeze_norm()
+
     def train_step(self, x, m, y, training=True, acc=None, inputs_ready=None, weight=1.0):
         """One iteration of STCGAN.run_epoch (STCGAN/stcgan.py:208-312): D step then G step.
         Returns the on-device loss scalars (no host sync).  The call order of every network
         (and so every BN running-statistics update) is the reference's; with ``streams`` the
         discriminator calls run on side streams (see _lanes) -- same kernels, same results."""
+        if training:
+            self._apply_freeze()  # (args.freeze_norm: a caller's .train() since the last step reset the norm layers)
         self.optim_D.zero_grad()
         self.optim_G.zero_grad()
         main, l1, l2 = self._lanes()
@@ -515,7 +537,8 @@ class STCGAN(object):
                 # G step's critical path (D update -> fake-input forwards -> their input gradients -> G backward)
                 # no longer waits for two forwards whose outputs nothing reads
                 # Instance norm has no running statistics: nothing can observe those calls, so they are not made
-                skip = unused and self.norm == "instance"
+                # ... nor with frozen BatchNorm statistics (args.freeze_norm), which those calls would not move
+                skip = unused and (self.norm == "instance" or self.freeze_norm)
                 late = unused and LATE_STATS_CALLS and not skip
                 if not late and not skip:
                     self.D1.stats_only = self.D2.stats_only = unused
@@ -647,6 +670,7 @@ class STCGAN(object):
     def run_epoch(self, training=True):
         for net in (self.G1, self.G2, self.D1, self.D2):
             net.train(training)
+        self._apply_freeze()
         if not training:  # eval-mode replicas use dev0's running statistics
             parallel.broadcast_buffers([self.G1, self.G2, self.D1, self.D2])
         self._lanes_stale = True  # (the broadcast above, a checkpoint load, a caller's writes between epochs)

@@ -24,23 +24,27 @@ channels, S[k] the block-k input resolution (S[1] = S[0]//2, S[k+1] = ceil(S[k]/
   y = tanh(convT_0(cr[0]) + bias), written NCHW fp32.
 
 norm_layer=nn.InstanceNorm2d (GenPlan.inorm / DiscPlan.inorm): the same buffers, with every
-"BN" above an instance norm -- a normed layer is the plain conv, then one ops.in_forward (statistics per sample over
-the stored raw output + the activation pass); its backward the input-gradient conv, then one ops.in_backward.  The
-BatchNorm path takes none of these calls.
+"BN" above an instance norm -- a normed layer is the plain conv, then one instance-norm forward (statistics per sample
+over the stored raw output + the activation pass); its backward the input-gradient conv, then one instance-norm
+backward.  The BatchNorm path takes none of these calls.
 
 BatchNorm layers on their running statistics (eval mode, or norm children frozen under a train-mode network;
-DESIGN.md section 8e): conv, the eval table (+ rstd_run when a backward follows) and ops.bn_apply forward; backward the
-input-gradient conv, then one ops.bn_backward_frozen (one pass; the sums only where parameter gradients are wanted).
+DESIGN.md section 8e): conv, the eval table (+ rstd_run when a backward follows) and the apply pass forward; backward
+the input-gradient conv, then one frozen-statistics backward (one pass; the sums only where parameter gradients are
+wanted).
+
+Every place where a conv meets a norm layer goes through two functions, whatever the norm and its mode (_IN, _BATCH,
+_RUNNING): _conv_norm_act forward and _conv_act_norm_backward backward, which name the library calls of each form.
+The latter is also the one place where a conv's weight is released to the optimiser (GradWriter.done) after its last
+read.
 """
+import typing
+
 import torch
 
 from . import _lib as L
 from . import ops
 from .ops import LRELU
-
-# ----------------------------------------------------------------------------- helpers
-
-
 
 # ----------------------------------------------------------------------------- tracing (tests)
 # TRACE: None, or a dict that collects, per network call, the forward's saved buffers and the backward's
@@ -84,7 +88,9 @@ _set_stream = torch._C._cuda_setStream
 
 
 def _stream_wait(waiter_h, src_h):
-    return L.lib().stc_stream_wait(waiter_h, src_h)
+    """Stream ``waiter_h`` waits for what is queued on ``src_h`` (raw handles), through one library call
+    (stc_stream_wait: a pooled event that outlives an open capture)."""
+    L.check(L.lib().stc_stream_wait(waiter_h, src_h), "stc_stream_wait")
 
 # Events recorded or waited on while a HIP graph is being captured, kept alive until the capture has ended
 # (STCGAN.capture sets a list here and drops it after capture_end).  torch's Stream.wait_stream and a fork's local
@@ -101,9 +107,8 @@ def hold(ev):
 
 
 def wait_stream(waiter, src):
-    """waiter.wait_stream(src), through one library call (stc_stream_wait: a pooled event that outlives an open
-    capture)."""
-    L.check(L.lib().stc_stream_wait(waiter.cuda_stream, src.cuda_stream), "stc_stream_wait")
+    """waiter.wait_stream(src), as _stream_wait."""
+    _stream_wait(waiter.cuda_stream, src.cuda_stream)
 
 
 class _WgradLane:
@@ -134,7 +139,7 @@ class _WgradLane:
             return fn()
         self.last_side = True
         side, cur = self.side, self.cur
-        L.check(_stream_wait(self._side_h, self._cur_h), "stc_stream_wait")
+        _stream_wait(self._side_h, self._cur_h)
         for t in reads:
             t.record_stream(side)
         _set_stream(side.stream_id, side.device_index, side.device_type)
@@ -145,7 +150,7 @@ class _WgradLane:
 
     def join(self):
         if self.side is not None:
-            L.check(_stream_wait(self._cur_h, self._side_h), "stc_stream_wait")
+            _stream_wait(self._cur_h, self._side_h)
 
 
 class GradWriter:
@@ -187,7 +192,7 @@ class GradWriter:
             return
         fresh = [p for p in params if id(p) not in self._acc_ids]
         if fresh:
-            side = lane.side if (lane is not None and getattr(lane, "last_side", False)) else None
+            side = lane.side if (lane is not None and lane.last_side) else None
             self.exchange.ready(fresh, side)
 
     def flush(self):
@@ -284,42 +289,112 @@ def _check_plane(B, C, h, w):
                          f"torch.Size([{B}, {C}, {h}, {w}])")
 
 
-def _conv_in_act(kind, B, xv, cin, w, cout, yv, dt, norm, apply_x, y1, s1, y2=None, s2=0.0):
-    """Conv -> InstanceNorm2d -> activation pass of ``apply_x`` into y1 [and y2]: the plain conv, then one
-    ops.in_forward (statistics of the stored raw output; the same in train and eval).  Returns (mean, rstd)."""
+# ----------------------------------------------------------------------------- the normed-layer step
+# How the norm layers of one network call normalise: instance norm (one mode); BatchNorm on batch statistics;
+# BatchNorm on its running statistics (eval mode, or frozen under a train-mode network).
+_IN, _BATCH, _RUNNING = 0, 1, 2
+
+
+def _norm_mode(plan, batch_stats):
+    return _IN if plan.inorm else (_BATCH if batch_stats else _RUNNING)
+
+
+def _conv_norm_act(kind, B, xv, cin, w, cout, yv, dt, norm, mode, apply_x, y1, s1, y2, s2, drop, defer, keep):
+    """Conv into ``yv`` -> norm layer ``norm`` -> activation pass of ``apply_x`` (yv or its top-left crop) into y1 [and
+    y2] (y1 None: no pass).  Returns ((2, cout) scale / shift table or None, (mean, rstd) or None).
+    _BATCH: one library call, the statistics out of the conv itself; ``defer`` (a list): the running statistics are not
+    updated, the update's inputs are appended (bn_running_update).  _RUNNING: conv, the table from the running
+    statistics, the apply pass; ``keep`` (a backward will follow): (running_mean, rstd_run) beside the table.  _IN:
+    conv, then the statistics of the stored raw output with the pass; no table.  ``drop``: a dropout level between a
+    BatchNorm and the activation (dropout_next)."""
+    if mode == _BATCH:
+        return ops.conv_bn_act(kind, B, xv, cin, w, cout, yv, dt, norm, apply_x, y1, s1, y2, s2, defer, drop)
     ops.conv(kind, B, xv, cin, w, cout, yv, dt)
-    return ops.in_forward(B, yv, cout, dt, norm, apply_x, y1, s1, y2, s2)
-
-
-def _conv_bn(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev, keep=False):
-    """Conv whose output feeds a BatchNorm2d: returns ((2, cout) scale/shift table, (mean, rstd) or None).
-    Train mode (batch statistics): they come out of the conv itself (stc_conv_fwd_ex).  Otherwise the table is built
-    from the running statistics; ``keep`` (a backward will follow): (running_mean, rstd_run) beside it."""
-    t = torch.empty((2, cout), dtype=torch.float32, device=dev)
-    if train:
-        part, nch = ops.conv_stats(kind, B, xv, cin, w, cout, yv, dt)
-        st = ops.bn_finalize_part(part, nch, cout, bn, t[0], t[1])
-    else:
-        ops.conv(kind, B, xv, cin, w, cout, yv, dt)
-        ops.bn_eval_table(cout, bn, t[0], t[1])
-        st = (bn.running_mean, ops.bn_running_rstd(cout, bn)) if keep else None
-    return t, st
-
-
-def _conv_bn_act(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev, apply_x, y1, s1, y2=None, s2=0.0, defer=None,
-                 drop=None, keep=False):
-    """Conv -> BatchNorm2d -> activation pass of ``apply_x`` into y1 [and y2] (y1 None: none); returns _conv_bn's
-    (table, (mean, rstd) or None).  ``train``: the layer uses batch statistics -- one library call
-    (ops.conv_bn_act); ``defer`` (a list): the running statistics are not updated, the update's inputs are appended
-    (ops.bn_running_update).  Otherwise (running statistics: eval mode, or frozen norm layers) conv, table and
-    ops.bn_apply, ``defer`` ignored and ``keep`` as in _conv_bn.  ``drop``: a dropout level between the BatchNorm and
-    the activation (ops.dropout_next), in either form."""
-    if train:
-        return ops.conv_bn_act(kind, B, xv, cin, w, cout, yv, dt, bn, apply_x, y1, s1, y2, s2, defer=defer, drop=drop)
-    t, st = _conv_bn(kind, B, xv, cin, w, cout, yv, dt, bn, train, dev, keep=keep)
+    if mode == _IN:
+        return None, ops.in_forward(B, yv, cout, dt, norm, apply_x, y1, s1, y2, s2)
+    t = torch.empty((2, cout), dtype=torch.float32, device=w.device)
+    ops.bn_eval_table(cout, norm, t[0], t[1])
+    st = (norm.running_mean, ops.bn_running_rstd(cout, norm)) if keep else None
     if y1 is not None:
-        ops.bn_apply(B, apply_x, cout, dt, (t[0], t[1]), y1, s1, y2, s2, drop=drop)
+        ops.bn_apply(B, apply_x, cout, dt, (t[0], t[1]), y1, s1, y2, s2, drop)
     return t, st
+
+
+def _conv_act_norm_backward(kind, B, gv, cg, wd, cin, gt, yv, dt, norm, mode, tab, st, xv, C, s_self, g_other, s_other,
+                            ch_off, dxv, drop, own, W, lane):
+    """The backward of one layer boundary: the input-gradient conv (kind, gv with cg channels, packed weight wd, cin
+    output channels) into the view ``yv`` of tensor ``gt``, then the backward of the activation(s) and of the norm
+    layer ``norm`` (None: none) that produced the conv's input, into ``dxv``.  xv: the norm's input (C channels),
+    (tab, st) what _conv_norm_act returned for it.  The norm's output fed this conv through an activation of slope
+    s_self and, where ``g_other`` is given, another consumer through one of slope s_other.  The conv's own gradient as
+    the norm sees it is ``gt`` at channel ch_off over xv's extent.
+
+    ``own``: the conv's parameters; W.done(own, lane) right after the last read of the weight: from there the
+    optimiser may update it and, under data parallelism, the exchange may start on its gradient.  Then the norm's own.
+
+    norm None              the activation backward in the conv epilogue where there is one, else conv + bn_backward
+    _IN                    conv, in_backward
+    _RUNNING               conv, bn_backward_frozen (through ``drop`` where there is one)
+    _BATCH with ``drop``   conv, bn_backward (the GEMM epilogues know nothing of the mask)
+    _BATCH                 the BatchNorm reduction fused into the conv (conv_bn_backward)"""
+    if norm is None:
+        # (no epilogue form under TRACE, which wants the conv's own output, or where the conv writes a larger extent
+        # than the activation's: an odd generator level)
+        if (TRACE is None and yv.H == xv.H and yv.W == xv.W
+                and ops.conv_act_backward(kind, B, gv, cg, wd, cin, dxv, dt, xv, s_self, g_other, s_other)):
+            if W is not None:
+                W.done(own, lane)
+            return
+        fused = False
+    else:
+        fused = mode == _BATCH and drop is None
+    if not fused:
+        ops.conv(kind, B, gv, cg, wd, cin, yv, dt)
+        if W is not None and norm is not None:
+            W.done(own, lane)
+        # the kernels form g1 * act1' + g2 * act2' in this order: another consumer's gradient first
+        g1, s1, g2, s2 = L.nhwc_view(gt, ch_off, xv.H, xv.W), s_self, None, 0.0
+        if g_other is not None:
+            g1, s1, g2, s2 = g_other, s_other, g1, s1
+        if norm is None:
+            ops.bn_backward(B, xv, C, dt, dxv, g1, s1, g2, s2)
+            if W is not None:
+                W.done(own, lane)
+            return
+    # where the affine parameters' gradients go: nowhere when they are not wanted or the norm has none
+    dgamma = dbeta = None
+    if W is not None and norm.weight is not None:
+        dgamma, dbeta = W.dest(norm.weight), W.dest(norm.bias)
+    if fused:
+        ops.conv_bn_backward(kind, B, gv, cg, wd, cin, yv, dt, xv, C, (tab[0], tab[1], st[0], st[1]), norm.weight,
+                             s_self, ch_off, g_other, s_other, dxv, dgamma, dbeta)
+        if W is not None:
+            W.done(own, lane)
+    elif mode == _IN:
+        ops.in_backward(B, xv, C, dt, dxv, norm, st, g1, s1, g2, s2, dgamma, dbeta)
+    elif mode == _RUNNING:
+        ops.bn_backward_frozen(B, xv, C, dt, dxv, g1, s1, g2, s2, (tab[0], tab[1], st[0], st[1]), dgamma, dbeta,
+                               W is not None, drop)
+    else:
+        ops.bn_backward(B, xv, C, dt, dxv, g1, s1, g2, s2, (tab[0], tab[1], st[0], st[1], norm.weight), dgamma, dbeta,
+                        drop)
+    if dgamma is not None:
+        W.done([norm.weight, norm.bias])
+
+
+def _input_grads(B, gv, cg, weight, saved, hw, need_src, dt, cache, dev):
+    """The tail of a backward: the first layer's input-gradient conv (gradient view gv, cg channels) into a padded
+    NHWC tensor, scattered into one NCHW fp32 gradient per source that needs one (None for the others)."""
+    cin_pad = saved["cin_pad"]
+    wd = ops.packed(cache, weight, L.PACK_CONV_DGRAD, cin_pad, cg, dt)
+    gx = _nhwc(B, 2 * gv.H, 2 * gv.W, cin_pad, dt, dev)
+    ops.conv(L.CONVT_S2, B, gv, cg, wd, cin_pad, L.nhwc_view(gx), dt)
+    H, W_ = hw
+    # only the sources that need a gradient; the scatter writes every element of those
+    src_grads = [torch.empty((B, c, H, W_), dtype=torch.float32, device=dev) if nd else None
+                 for c, nd in zip(saved["src_c"], need_src)]
+    ops.scatter(gx, src_grads, saved["src_c"], dt, H, W_)
+    return src_grads
 
 
 # ----------------------------------------------------------------------------- generator
@@ -352,11 +427,7 @@ def gen_forward(plan, sources, train, dt, cache, save, batch_stats=None):
     cr = [_nhwc(B, *S[k + 1], cin_t(k), dt, dev) for k in range(Lv)]
     rq = [None] + [_nhwc(B, *_pad2(S, k), co[k - 1], dt, dev) for k in range(1, Lv)]
     tab_d, tab_u, st_d, st_u = {}, {}, {}, {}
-
-    def conv_bn_act(kind, xv, cin_, w, cout, yv, bn, apply_x, y1, s1, y2=None, s2=0.0, drop=None):
-        """conv -> BatchNorm (batch statistics fused into the conv in train mode) -> activation pass."""
-        return _conv_bn_act(kind, B, xv, cin_, w, cout, yv, dt, bn, batch_stats, dev, apply_x, y1, s1, y2, s2,
-                            drop=drop, keep=save)
+    mode = _norm_mode(plan, batch_stats)
 
     # use_dropout, train mode: this call's {seed, offset} copy (one tiny launch; the generator's offset advances),
     # read from device memory by every dropout kernel of the call, forward and backward
@@ -370,39 +441,36 @@ def gen_forward(plan, sources, train, dt, cache, save, batch_stats=None):
 
     # ---- down path
     w0 = ops.packed(cache, plan.conv[0].weight, L.PACK_CONV_FWD, co[0], cin_pad, dt)
-    if ops.conv_act(L.CONV_S2, B, L.nhwc_view(xin), cin_pad, w0, co[0], L.nhwc_view(ad[0]), LRELU, dt,
-                    L.nhwc_view(cr[0], 0), 0.0):
+    xv, av, sv = L.nhwc_view(xin), L.nhwc_view(ad[0]), L.nhwc_view(cr[0], 0)  # conv input, its activation, the skip
+    if ops.conv_act(L.CONV_S2, B, xv, cin_pad, w0, co[0], av, LRELU, dt, sv, 0.0):
         # no raw r_0: its only reader, the backward's ReLU/LeakyReLU test, sees the same signs in ad[0]
         rd[0] = ad[0]
     else:
         rd[0] = _nhwc(B, *S[1], co[0], dt, dev)
-        ops.conv(L.CONV_S2, B, L.nhwc_view(xin), cin_pad, w0, co[0], L.nhwc_view(rd[0]), dt)
-        ops.bn_apply(B, L.nhwc_view(rd[0]), co[0], dt, None, L.nhwc_view(ad[0]), LRELU,
-                     L.nhwc_view(cr[0], 0), 0.0)
+        rv = L.nhwc_view(rd[0])
+        ops.conv(L.CONV_S2, B, xv, cin_pad, w0, co[0], rv, dt)
+        ops.bn_apply(B, rv, co[0], dt, None, av, LRELU, sv, 0.0)
     for k in range(1, Lv):
         wk = ops.packed(cache, plan.conv[k].weight, L.PACK_CONV_FWD, co[k], co[k - 1], dt)
-        if k <= Lv - 2 and plan.inorm:
-            rv = L.nhwc_view(rd[k])
-            st_d[k] = _conv_in_act(L.CONV_S2, B, L.nhwc_view(ad[k - 1]), co[k - 1], wk, co[k], rv, dt, plan.bnd[k], rv,
-                                   L.nhwc_view(ad[k]), LRELU, L.nhwc_view(cr[k], 0), 0.0)
-        elif k <= Lv - 2:
-            rv = L.nhwc_view(rd[k])
-            tab_d[k], st_d[k] = conv_bn_act(L.CONV_S2, L.nhwc_view(ad[k - 1]), co[k - 1], wk, co[k], rv, plan.bnd[k],
-                                            rv, L.nhwc_view(ad[k]), LRELU, L.nhwc_view(cr[k], 0), 0.0)
+        xv, rv = av, L.nhwc_view(rd[k])  # (conv_k reads the activation the level above wrote)
+        if k <= Lv - 2:
+            av = L.nhwc_view(ad[k])
+            t, st_d[k] = _conv_norm_act(L.CONV_S2, B, xv, co[k - 1], wk, co[k], rv, dt, plan.bnd[k], mode, rv, av,
+                                        LRELU, L.nhwc_view(cr[k], 0), 0.0, None, None, save)
+            if t is not None:
+                tab_d[k] = t
         else:  # innermost: no down-norm (STCGAN/networks.py:118-124)
-            ops.conv(L.CONV_S2, B, L.nhwc_view(ad[k - 1]), co[k - 1], wk, co[k], L.nhwc_view(rd[k]), dt)
-            ops.bn_apply(B, L.nhwc_view(rd[k]), co[k], dt, None, L.nhwc_view(cr[k]), 0.0)
+            ops.conv(L.CONV_S2, B, xv, co[k - 1], wk, co[k], rv, dt)
+            ops.bn_apply(B, rv, co[k], dt, None, L.nhwc_view(cr[k]), 0.0)
     # ---- up path
     for k in range(Lv - 1, 0, -1):
         wt = ops.packed(cache, plan.convT[k].weight, L.PACK_CONVT_FWD, co[k - 1], cin_t(k), dt)
         # statistics over the full ConvT extent (before the crop of an odd level)
-        if plan.inorm:
-            st_u[k] = _conv_in_act(L.CONVT_S2, B, L.nhwc_view(cr[k]), cin_t(k), wt, co[k - 1], L.nhwc_view(rq[k]), dt,
-                                   plan.bnu[k], L.nhwc_view(rq[k], 0, *S[k]), L.nhwc_view(cr[k - 1], co[k - 1]), 0.0)
-            continue
-        tab_u[k], st_u[k] = conv_bn_act(L.CONVT_S2, L.nhwc_view(cr[k]), cin_t(k), wt, co[k - 1], L.nhwc_view(rq[k]),
-                                        plan.bnu[k], L.nhwc_view(rq[k], 0, *S[k]), L.nhwc_view(cr[k - 1], co[k - 1]),
-                                        0.0, drop=drop_of(k))
+        t, st_u[k] = _conv_norm_act(L.CONVT_S2, B, L.nhwc_view(cr[k]), cin_t(k), wt, co[k - 1], L.nhwc_view(rq[k]), dt,
+                                    plan.bnu[k], mode, L.nhwc_view(rq[k], 0, *S[k]),
+                                    L.nhwc_view(cr[k - 1], co[k - 1]), 0.0, None, 0.0, drop_of(k), None, save)
+        if t is not None:
+            tab_u[k] = t
     # ---- outermost: tanh(convT_0(cr[0]) + bias) -> NCHW fp32
     Ho, Wo = 2 * S[1][0], 2 * S[1][1]
     y = torch.empty((B, plan.out_c, Ho, Wo), dtype=torch.float32, device=dev)
@@ -434,20 +502,12 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
     need_w = W is not None
     lane = _WgradLane() if need_w else None
     drops = saved.get("drop") or {}  # {level: dropout level of the forward call} (use_dropout, train mode)
-    frozen = saved["frozen"]  # the BatchNorm layers normalised with their running statistics
-
-    def dest(p):
-        return W.dest(p) if need_w else None
-
-    def dest_opt(p):
-        """dest of an affine parameter that a norm layer may not have."""
-        return W.dest(p) if (need_w and p is not None) else None
-
+    mode = _norm_mode(plan, not saved["frozen"])
     # ---- tanh + bias
     cp = ops.vec(dt)
     Ho, Wo = y.shape[2], y.shape[3]
     dq = _nhwc(B, Ho, Wo, cp, dt, dev)
-    ops.tanh_bias_bwd(y, gy, L.nhwc_view(dq), dt, dbias=dest(plan.convT[0].bias))
+    ops.tanh_bias_bwd(y, gy, L.nhwc_view(dq), dt, dbias=W.dest(plan.convT[0].bias) if need_w else None)
     if need_w:
         W.done([plan.convT[0].bias])
     _trace("G", ("dq", 0), dq)
@@ -458,78 +518,29 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
         cout_t = plan.out_c if k == 0 else co[k - 1]
         cg = cp if k == 0 else cout_t
         dqv = L.nhwc_view(dq)
+        wT = plan.convT[k].weight
         if need_w:  # D = convT input (grid S[k+1]), G = dq gathered at stride 2
-            wT = plan.convT[k].weight
-            lane.run(lambda k=k, dqv=dqv, cin_t=cin_t, cg=cg, cout_t=cout_t, out=W.dest(wT): ops.wgrad(
-                B, 2, L.nhwc_view(cr[k]), cin_t, dqv, cg, cout_t, dt, device=dev, out=out), dq,
-                pixels=S[k + 1][0] * S[k + 1][1])
-        wd = ops.packed(cache, plan.convT[k].weight, L.PACK_CONVT_DGRAD, cin_t, cg, dt)
-        if k < Lv - 1:
-            ah, aw = _pad2(S, k + 1)
-            gcat[k] = _nhwc(B, ah, aw, cin_t, dt, dev, zero=(ah, aw) != S[k + 1])
-        else:
-            gcat[k] = _nhwc(B, *S[Lv], cin_t, dt, dev)
-        _trace("G", ("gcat", k), gcat[k])
+            out = W.dest(wT)
+            lane.run(lambda: ops.wgrad(B, 2, L.nhwc_view(cr[k]), cin_t, dqv, cg, cout_t, dt, device=dev, out=out), dq,
+                     pixels=S[k + 1][0] * S[k + 1][1])
+        wd = ops.packed(cache, wT, L.PACK_CONVT_DGRAD, cin_t, cg, dt)
         if k == Lv - 1:
+            gcat[k] = _nhwc(B, *S[Lv], cin_t, dt, dev)
+            _trace("G", ("gcat", k), gcat[k])
             ops.conv(L.CONV_S2, B, dqv, cg, wd, cin_t, L.nhwc_view(gcat[k], 0, *S[k + 1]), dt)
             if need_w:  # (after the last read of the weight: the optimiser may update it from here on)
-                W.done([plan.convT[k].weight], lane)
+                W.done([wT], lane)
             break
         # BN_up[k+1] over q_{k+1}: full (padded) extent; the cropped rows carry zero gradient.
-        # Its gradient is the second half of gcat[k] (ReLU of the concat), so the BN reduction
-        # is fused into the conv that writes gcat[k] (channels C..2C -> BN channels 0..C).
+        # Its gradient is the second half of gcat[k] (ReLU of the concat: channels C..2C -> BN channels 0..C)
         ah, aw = _pad2(S, k + 1)
+        gcat[k] = _nhwc(B, ah, aw, cin_t, dt, dev, zero=(ah, aw) != S[k + 1])
+        _trace("G", ("gcat", k), gcat[k])
         C = co[k]
         dq = _nhwc(B, ah, aw, C, dt, dev)
-        bn = plan.bnu[k + 1]
-        if plan.inorm:
-            # instance norm: the unfused form -- the conv writes gcat[k], then one fused ReLU + norm backward
-            ops.conv(L.CONV_S2, B, dqv, cg, wd, cin_t, L.nhwc_view(gcat[k], 0, *S[k + 1]), dt)
-            if need_w:
-                W.done([plan.convT[k].weight], lane)
-            ops.in_backward(B, L.nhwc_view(rq[k + 1]), C, dt, L.nhwc_view(dq), bn, st_u[k + 1],
-                            g1=L.nhwc_view(gcat[k], C), s1=0.0, dgamma=dest_opt(bn.weight), dbeta=dest_opt(bn.bias))
-            if need_w and plan.affine:
-                W.done([bn.weight, bn.bias])
-            _trace("G", ("dq", k + 1), dq)
-            continue
-        mean, rstd = st_u[k + 1]
-        t = tab_u[k + 1]
-        drop = drops.get(k + 1)
-        if frozen:
-            # running statistics: the unfused form -- the conv writes gcat[k], then the one-pass backward (dx needs
-            # no batch sum; the sums only where parameter gradients are wanted), through the dropout where there is one
-            ops.conv(L.CONV_S2, B, dqv, cg, wd, cin_t, L.nhwc_view(gcat[k], 0, *S[k + 1]), dt)
-            if need_w:
-                W.done([plan.convT[k].weight], lane)
-            ops.bn_backward_frozen(B, L.nhwc_view(rq[k + 1]), C, dt, L.nhwc_view(dq), g1=L.nhwc_view(gcat[k], C),
-                                   s1=0.0, state=(t[0], t[1], mean, rstd), dgamma=dest(bn.weight),
-                                   dbeta=dest(bn.bias), want_params=need_w, drop=drop)
-            if need_w:
-                W.done([bn.weight, bn.bias])
-            _trace("G", ("dq", k + 1), dq)
-            continue
-        if drop is not None:
-            # a dropout level: the gradient reaches BN_up[k+1]'s output through the mask, g * [n > 0] * keep/(1-p).
-            # The unfused form -- the conv writes gcat[k], then the dropout-aware BN backward recomputes the mask
-            # from the call's counter (the GEMM epilogues know nothing of it; two small element-wise launches more)
-            ops.conv(L.CONV_S2, B, dqv, cg, wd, cin_t, L.nhwc_view(gcat[k], 0, *S[k + 1]), dt)
-            if need_w:
-                W.done([plan.convT[k].weight], lane)
-            ops.bn_backward(B, L.nhwc_view(rq[k + 1]), C, dt, L.nhwc_view(dq), g1=L.nhwc_view(gcat[k], C), s1=0.0,
-                            bn_state=(t[0], t[1], mean, rstd, bn.weight), dgamma=dest(bn.weight),
-                            dbeta=dest(bn.bias), drop=drop)
-            if need_w:
-                W.done([bn.weight, bn.bias])
-            _trace("G", ("dq", k + 1), dq)
-            continue
-        ops.conv_bn_backward(L.CONV_S2, B, dqv, cg, wd, cin_t, L.nhwc_view(gcat[k], 0, *S[k + 1]), dt,
-                             bn_x=L.nhwc_view(rq[k + 1]), C=C, bn_state=(t[0], t[1], mean, rstd),
-                             gamma=bn.weight, s_self=0.0, ch_off=C, dxv=L.nhwc_view(dq),
-                             dgamma=dest(bn.weight), dbeta=dest(bn.bias))
-        if need_w:
-            W.done([plan.convT[k].weight], lane)
-            W.done([bn.weight, bn.bias])
+        _conv_act_norm_backward(L.CONV_S2, B, dqv, cg, wd, cin_t, gcat[k], L.nhwc_view(gcat[k], 0, *S[k + 1]), dt,
+                                plan.bnu[k + 1], mode, tab_u.get(k + 1), st_u[k + 1], L.nhwc_view(rq[k + 1]), C, 0.0,
+                                None, 0.0, C, L.nhwc_view(dq), drops.get(k + 1), [wT], W, lane)
         _trace("G", ("dq", k + 1), dq)
     # ---- innermost r_{L-1}: ReLU backward (no BN)
     dr = _nhwc(B, *S[Lv], co[Lv - 1], dt, dev)
@@ -540,81 +551,31 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
     for k in range(Lv - 1, -1, -1):
         drv = L.nhwc_view(dr)
         _trace("G", ("dr", k), dr)
+        wk = plan.conv[k].weight
         if k == 0:
             if need_w:
-                w0 = plan.conv[0].weight
-                lane.run(lambda drv=drv, out=W.dest(w0): ops.wgrad(
-                    B, 2, drv, co[0], L.nhwc_view(xin), saved["cin_pad"], saved["cin"], dt, device=dev, out=out),
-                    dr, pixels=S[1][0] * S[1][1])
+                out = W.dest(wk)
+                lane.run(lambda: ops.wgrad(B, 2, drv, co[0], L.nhwc_view(xin), saved["cin_pad"], saved["cin"], dt,
+                                           device=dev, out=out), dr, pixels=S[1][0] * S[1][1])
             if need_src:
-                wd = ops.packed(cache, plan.conv[0].weight, L.PACK_CONV_DGRAD, saved["cin_pad"], co[0], dt)
-                gx = _nhwc(B, 2 * S[1][0], 2 * S[1][1], saved["cin_pad"], dt, dev)
-                ops.conv(L.CONVT_S2, B, drv, co[0], wd, saved["cin_pad"], L.nhwc_view(gx), dt)
-                H, W_ = S[0]
-                # only the sources that need a gradient; the scatter writes every element of those
-                src_grads = [torch.empty((B, c, H, W_), dtype=torch.float32, device=dev) if nd else None
-                             for c, nd in zip(saved["src_c"], need_src)]
-                ops.scatter(gx, src_grads, saved["src_c"], dt, H, W_)
+                src_grads = _input_grads(B, drv, co[0], wk, saved, S[0], need_src, dt, cache, dev)
             if need_w:
-                W.done([plan.conv[0].weight], lane)
+                W.done([wk], lane)
             break
-        cprev = co[k - 1]
+        j, cprev = k - 1, co[k - 1]
         if need_w:  # D = dr_k (grid S[k+1]), G = conv_k input = ad[k-1]
-            wk = plan.conv[k].weight
-            lane.run(lambda k=k, drv=drv, cprev=cprev, out=W.dest(wk): ops.wgrad(
-                B, 2, drv, co[k], L.nhwc_view(ad[k - 1]), cprev, cprev, dt, device=dev, out=out), dr,
-                pixels=S[k + 1][0] * S[k + 1][1])
-        wd = ops.packed(cache, plan.conv[k].weight, L.PACK_CONV_DGRAD, cprev, co[k], dt)
+            out = W.dest(wk)
+            lane.run(lambda: ops.wgrad(B, 2, drv, co[k], L.nhwc_view(ad[j]), cprev, cprev, dt, device=dev, out=out), dr,
+                     pixels=S[k + 1][0] * S[k + 1][1])
+        wd = ops.packed(cache, wk, L.PACK_CONV_DGRAD, cprev, co[k], dt)
         ga = _nhwc(B, 2 * S[k + 1][0], 2 * S[k + 1][1], cprev, dt, dev)
         _trace("G", ("ga", k), ga)
-        # r_{k-1} feeds the skip (ReLU) and conv_k (LeakyReLU); then BN_down[k-1] (absent for k-1 == 0)
+        # r_{k-1} feeds the skip (ReLU; its gradient the first half of gcat[k-1]) and conv_k (LeakyReLU; ga, cropped
+        # to S[k]); then BN_down[k-1] (absent for k-1 == 0)
         dr = _nhwc(B, *S[k], cprev, dt, dev)
-        xv = L.nhwc_view(rd[k - 1])
-        g1 = L.nhwc_view(gcat[k - 1], 0, *S[k])
-        if k - 1 == 0:
-            # r_0 has no BatchNorm: the activation backward (LeakyReLU into conv_1, ReLU into the skip) in the
-            # input-gradient conv's epilogue when it has one (no ga tensor), else conv + bn_backward
-            if TRACE is not None or (ga.shape[1], ga.shape[2]) != tuple(S[k]) or not ops.conv_act_backward(
-                    L.CONVT_S2, B, drv, co[k], wd, cprev, L.nhwc_view(dr), dt, act_x=xv, s_self=LRELU, g_other=g1,
-                    s_other=0.0):
-                ops.conv(L.CONVT_S2, B, drv, co[k], wd, cprev, L.nhwc_view(ga), dt)
-                ops.bn_backward(B, xv, cprev, dt, L.nhwc_view(dr), g1=g1, s1=0.0, g2=L.nhwc_view(ga, 0, *S[k]),
-                                s2=LRELU)
-            if need_w:
-                W.done([plan.conv[k].weight], lane)
-        elif plan.inorm:  # the conv writes ga, then one fused ReLU / LeakyReLU + instance-norm backward
-            bn = plan.bnd[k - 1]
-            ops.conv(L.CONVT_S2, B, drv, co[k], wd, cprev, L.nhwc_view(ga), dt)
-            if need_w:
-                W.done([plan.conv[k].weight], lane)
-            ops.in_backward(B, xv, cprev, dt, L.nhwc_view(dr), bn, st_d[k - 1], g1=g1, s1=0.0,
-                            g2=L.nhwc_view(ga, 0, *S[k]), s2=LRELU, dgamma=dest_opt(bn.weight),
-                            dbeta=dest_opt(bn.bias))
-            if need_w and plan.affine:
-                W.done([bn.weight, bn.bias])
-        elif frozen:  # the conv writes ga, then the one-pass ReLU / LeakyReLU + frozen-BatchNorm backward
-            mean, rstd = st_d[k - 1]
-            t = tab_d[k - 1]
-            bn = plan.bnd[k - 1]
-            ops.conv(L.CONVT_S2, B, drv, co[k], wd, cprev, L.nhwc_view(ga), dt)
-            if need_w:
-                W.done([plan.conv[k].weight], lane)
-            ops.bn_backward_frozen(B, xv, cprev, dt, L.nhwc_view(dr), g1=g1, s1=0.0, g2=L.nhwc_view(ga, 0, *S[k]),
-                                   s2=LRELU, state=(t[0], t[1], mean, rstd), dgamma=dest(bn.weight),
-                                   dbeta=dest(bn.bias), want_params=need_w)
-            if need_w:
-                W.done([bn.weight, bn.bias])
-        else:  # BN reduction fused into the input-gradient conv that produces ga
-            mean, rstd = st_d[k - 1]
-            t = tab_d[k - 1]
-            bn = plan.bnd[k - 1]
-            ops.conv_bn_backward(L.CONVT_S2, B, drv, co[k], wd, cprev, L.nhwc_view(ga), dt, bn_x=xv, C=cprev,
-                                 bn_state=(t[0], t[1], mean, rstd), gamma=bn.weight, s_self=LRELU,
-                                 g_other=g1, s_other=0.0, dxv=L.nhwc_view(dr), dgamma=dest(bn.weight),
-                                 dbeta=dest(bn.bias))
-            if need_w:
-                W.done([plan.conv[k].weight], lane)
-                W.done([bn.weight, bn.bias])
+        _conv_act_norm_backward(L.CONVT_S2, B, drv, co[k], wd, cprev, ga, L.nhwc_view(ga), dt, plan.bnd.get(j), mode,
+                                tab_d.get(j), st_d.get(j), L.nhwc_view(rd[j]), cprev, LRELU,
+                                L.nhwc_view(gcat[j], 0, *S[k]), 0.0, 0, L.nhwc_view(dr), None, [wk], W, lane)
     if lane is not None:
         lane.join()
     return src_grads
@@ -684,6 +645,8 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
             inputs[key] = xin
     raw, act, dims, chans, tabs, stats = [xin], [xin], [(H, W)], [cin_pad], [None], [None]
     out = None
+    mode = _norm_mode(plan, batch_stats)
+    xv = L.nhwc_view(xin)  # (of act[i], the input of conv_i)
     for i, cv in enumerate(plan.convs):
         s = plan.strides[i]
         if s == 2:
@@ -697,32 +660,28 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
                 out = torch.empty((B, cout, 0, 0), dtype=torch.float32, device=dev)
                 break
             out = torch.empty((B, cout, h, w), dtype=torch.float32, device=dev)
-            ops.conv(kind, B, L.nhwc_view(act[i]), chans[i], wp, cout, L.nchw_view(out), dt, bias=cv.bias,
-                     out_f32=True)
+            ops.conv(kind, B, xv, chans[i], wp, cout, L.nchw_view(out), dt, bias=cv.bias, out_f32=True)
             break
         tab, st = None, None
         a = _nhwc(B, h, w, cout, dt, dev)
-        if i >= 1 and plan.inorm:  # conv -> InstanceNorm -> LeakyReLU
-            assert cv.bias is None
-            o = _nhwc(B, h, w, cout, dt, dev)
-            ov = L.nhwc_view(o)
-            st = _conv_in_act(kind, B, L.nhwc_view(act[i]), chans[i], wp, cout, ov, dt, plan.bns[i - 1], ov,
-                              L.nhwc_view(a), LRELU)
-        elif i >= 1:  # conv -> BatchNorm -> LeakyReLU (networks.py:167-180); no conv bias there
+        av = L.nhwc_view(a)
+        if i >= 1:  # conv -> norm -> LeakyReLU (networks.py:167-180); no conv bias there
             assert cv.bias is None
             o = _nhwc(B, h, w, cout, dt, dev)
             ov = L.nhwc_view(o)
             # (stats_only: only the logits layer reads the last activation -- no pass)
-            t, st = _conv_bn_act(kind, B, L.nhwc_view(act[i]), chans[i], wp, cout, ov, dt, plan.bns[i - 1],
-                                 batch_stats, dev, ov, None if (stats_only and i == n - 2) else L.nhwc_view(a), LRELU,
-                                 defer=defer, keep=save)
-            tab = (t[0], t[1])
-        elif ops.conv_act(kind, B, L.nhwc_view(act[i]), chans[i], wp, cout, L.nhwc_view(a), LRELU, dt, bias=cv.bias):
+            t, st = _conv_norm_act(kind, B, xv, chans[i], wp, cout, ov, dt, plan.bns[i - 1], mode, ov,
+                                   None if (stats_only and i == n - 2) else av, LRELU, None, 0.0, None, defer, save)
+            if t is not None:
+                tab = (t[0], t[1])
+        elif ops.conv_act(kind, B, xv, chans[i], wp, cout, av, LRELU, dt, bias=cv.bias):
             o = a  # no raw output: the backward's LeakyReLU test sees the same signs in the activation
         else:
             o = _nhwc(B, h, w, cout, dt, dev)
-            ops.conv(kind, B, L.nhwc_view(act[i]), chans[i], wp, cout, L.nhwc_view(o), dt, bias=cv.bias)
-            ops.bn_apply(B, L.nhwc_view(o), cout, dt, tab, L.nhwc_view(a), LRELU)
+            ov = L.nhwc_view(o)
+            ops.conv(kind, B, xv, chans[i], wp, cout, ov, dt, bias=cv.bias)
+            ops.bn_apply(B, ov, cout, dt, None, av, LRELU)
+        xv = av
         raw.append(o)
         act.append(a)
         dims.append((h, w))
@@ -756,6 +715,7 @@ def disc_backward(plan, saved, gout, dt, cache, need_src, W):
     gch = cp
     src_grads = None
     lane = _WgradLane() if need_w else None
+    mode = _norm_mode(plan, not saved["frozen"])
     for i in range(n - 1, -1, -1):
         cv = plan.convs[i]
         s = plan.strides[i]
@@ -770,7 +730,7 @@ def disc_backward(plan, saved, gout, dt, cache, need_src, W):
             else:  # the weight gradient of the padded input (+ the constant-1 channel) goes through a scratch
                 dw_out, db_out = W.dest(cv.weight), W.dest(cv.bias)
 
-            def wg(i=i, s=s, cout=cout, gv=gv, gch=gch, cv=cv, bc=bc, dw_out=dw_out, db_out=db_out):
+            def wg():  # (run at once, by lane.run)
                 if bc is not None:  # the constant-1 channel's tap (1,1) is the bias gradient (disc_forward)
                     dW = ops.wgrad(B, s, gv, gch, L.nhwc_view(act[i]), chans[i], bc + 1, dt, device=dev, rows=cout)
                     dw_out.copy_(dW[:cout, :saved["cin"]])
@@ -784,14 +744,7 @@ def disc_backward(plan, saved, gout, dt, cache, need_src, W):
         own = [cv.weight] + ([cv.bias] if cv.bias is not None else [])
         if i == 0:
             if need_src:
-                wd = ops.packed(cache, cv.weight, L.PACK_CONV_DGRAD, saved["cin_pad"], gch, dt)
-                H, W_ = dims[0]
-                gx = _nhwc(B, 2 * h, 2 * w, saved["cin_pad"], dt, dev)
-                ops.conv(L.CONVT_S2, B, gv, gch, wd, saved["cin_pad"], L.nhwc_view(gx), dt)
-                # only the sources that need a gradient; the scatter writes every element of those
-                src_grads = [torch.empty((B, c, H, W_), dtype=torch.float32, device=dev) if nd else None
-                             for c, nd in zip(saved["src_c"], need_src)]
-                ops.scatter(gx, src_grads, saved["src_c"], dt, H, W_)
+                src_grads = _input_grads(B, gv, gch, cv.weight, saved, dims[0], need_src, dt, cache, dev)
             if need_w:
                 W.done(own, lane)
             break
@@ -805,51 +758,12 @@ def disc_backward(plan, saved, gout, dt, cache, need_src, W):
         else:
             wd = ops.packed(cache, cv.weight, L.PACK_CONV_S1_DGRAD, cin, gch, dt)
             dkind = L.CONV_S1_DGRAD
-        # through LeakyReLU (and the BN of layer i-1's output, when present: its reduction fused
-        # into the input-gradient conv)
+        # through LeakyReLU and the norm of layer i-1's output (none after layer 0)
         gn = _nhwc(B, ph, pw, cin, dt, dev)
         _trace("D", ("ga", i), ga)
-        xv = L.nhwc_view(raw[i])
-        if plan.inorm and stats[i] is not None:  # the conv writes ga, then LeakyReLU + instance-norm backward
-            bn = plan.bns[i - 2]
-            ops.conv(dkind, B, gv, gch, wd, cin, L.nhwc_view(ga), dt)
-            if need_w:
-                W.done(own, lane)
-            ops.in_backward(B, xv, cin, dt, L.nhwc_view(gn), bn, stats[i], g1=L.nhwc_view(ga), s1=LRELU,
-                            dgamma=W.dest(bn.weight) if (need_w and plan.affine) else None,
-                            dbeta=W.dest(bn.bias) if (need_w and plan.affine) else None)
-            if need_w and plan.affine:
-                W.done([bn.weight, bn.bias])
-        elif tabs[i] is None:  # (no BatchNorm: the LeakyReLU backward in the conv epilogue when it has one)
-            if TRACE is not None or not ops.conv_act_backward(dkind, B, gv, gch, wd, cin, L.nhwc_view(gn), dt, act_x=xv,
-                                                              s_self=LRELU):
-                ops.conv(dkind, B, gv, gch, wd, cin, L.nhwc_view(ga), dt)
-                ops.bn_backward(B, xv, cin, dt, L.nhwc_view(gn), g1=L.nhwc_view(ga), s1=LRELU)
-            if need_w:
-                W.done(own, lane)
-        elif saved["frozen"]:  # the conv writes ga, then the one-pass LeakyReLU + frozen-BatchNorm backward
-            mean, rstd = stats[i]
-            bn = plan.bns[i - 2]
-            ops.conv(dkind, B, gv, gch, wd, cin, L.nhwc_view(ga), dt)
-            if need_w:
-                W.done(own, lane)
-            ops.bn_backward_frozen(B, xv, cin, dt, L.nhwc_view(gn), g1=L.nhwc_view(ga), s1=LRELU,
-                                   state=(tabs[i][0], tabs[i][1], mean, rstd),
-                                   dgamma=W.dest(bn.weight) if need_w else None,
-                                   dbeta=W.dest(bn.bias) if need_w else None, want_params=need_w)
-            if need_w:
-                W.done([bn.weight, bn.bias])
-        else:
-            mean, rstd = stats[i]
-            bn = plan.bns[i - 2]
-            ops.conv_bn_backward(dkind, B, gv, gch, wd, cin, L.nhwc_view(ga), dt, bn_x=xv, C=cin,
-                                 bn_state=(tabs[i][0], tabs[i][1], mean, rstd), gamma=bn.weight,
-                                 s_self=LRELU, dxv=L.nhwc_view(gn),
-                                 dgamma=W.dest(bn.weight) if need_w else None,
-                                 dbeta=W.dest(bn.bias) if need_w else None)
-            if need_w:
-                W.done(own, lane)
-                W.done([bn.weight, bn.bias])
+        _conv_act_norm_backward(dkind, B, gv, gch, wd, cin, ga, L.nhwc_view(ga), dt,
+                                plan.bns[i - 2] if i >= 2 else None, mode, tabs[i], stats[i], L.nhwc_view(raw[i]), cin,
+                                LRELU, None, 0.0, 0, L.nhwc_view(gn), None, own, W, lane)
         g, gch, h, w = gn, cin, ph, pw
     if lane is not None:
         lane.join()
@@ -859,11 +773,23 @@ def disc_backward(plan, saved, gout, dt, cache, need_src, W):
 # ----------------------------------------------------------------------------- autograd
 
 
+class Ctrl(typing.NamedTuple):
+    """What one network call needs beside its tensors (NetFn's first input; networks._HipNet._run)."""
+    plan: object         # GenPlan / DiscPlan
+    kind: str            # "G" / "D"
+    train: bool          # the network's own training flag (dropout levels)
+    dt: torch.dtype      # compute dtype
+    cache: dict          # packed weights
+    nsrc: int            # number of sources among the tensor inputs
+    inputs: object       # dict reusing gathered discriminator inputs, or None
+    consumer: object     # stream that reads the source gradients, or None
+    stats_only: bool     # discriminator: only the running statistics are wanted
+    defer: object        # list collecting the running-statistics updates, or None
+    batch_stats: bool    # the BatchNorm modules' mode (networks._HipNet._batch_stats)
+
+
 class NetFn(torch.autograd.Function):
-    """One autograd node per network call.  inputs: (ctrl, *sources, *params); ctrl = (plan, kind, drop_on, dtype,
-    pack cache, sources, input cache, gradient consumer, stats_only, defer_running, batch_stats): drop_on = the
-    network's own training flag (dropout levels), batch_stats = its BatchNorm modules' (batch statistics and running
-    update, or running statistics; networks._HipNet._batch_stats).
+    """One autograd node per network call.  inputs: (ctrl, *sources, *params), ctrl a Ctrl.
 
     The backward returns gradients for the sources only: the parameters' gradients are written by the
     kernels straight into the network's flat gradient buffer (GradWriter), so autograd never allocates,
@@ -871,20 +797,22 @@ class NetFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ctrl, *tensors):
-        plan, kind, train, dt, cache, nsrc, inputs, _, stats_only, defer, batch_stats = ctrl
-        sources = [t.contiguous().float() for t in tensors[:nsrc]]
+        sources = [t.contiguous().float() for t in tensors[:ctrl.nsrc]]
         save = any(ctx.needs_input_grad[1:])  # (every mode: nothing under torch.no_grad())
-        ops.refresh_packs(cache)  # all operands packed since the last optimiser step, one launch
-        out, saved = (gen_forward(plan, sources, train, dt, cache, save, batch_stats) if kind == "G" else
-                      disc_forward(plan, sources, train, dt, cache, save, inputs, stats_only and not save, defer,
-                                   batch_stats))
+        ops.refresh_packs(ctrl.cache)  # all operands packed since the last optimiser step, one launch
+        if ctrl.kind == "G":
+            out, saved = gen_forward(ctrl.plan, sources, ctrl.train, ctrl.dt, ctrl.cache, save, ctrl.batch_stats)
+        else:
+            out, saved = disc_forward(ctrl.plan, sources, ctrl.train, ctrl.dt, ctrl.cache, save, ctrl.inputs,
+                                      ctrl.stats_only and not save, ctrl.defer, ctrl.batch_stats)
         ctx.ctrl = ctrl
         ctx.saved_net = saved
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        plan, kind, train, dt, cache, nsrc, _, consumer = ctx.ctrl[:8]
+        ctrl = ctx.ctrl
+        plan, nsrc, consumer = ctrl.plan, ctrl.nsrc, ctrl.consumer
         saved = ctx.saved_net
         if saved is None:
             raise RuntimeError("stcgan_amd: this network call saved nothing for a backward (a second backward "
@@ -898,8 +826,8 @@ class NetFn(torch.autograd.Function):
             # from handing the block back to the main stream once this Python call returns, while the
             # kernels enqueued here may still read it
             gout.record_stream(torch.cuda.current_stream(gout.device))
-        bwd = gen_backward if kind == "G" else disc_backward
-        src_grads = bwd(plan, saved, gout, dt, cache, need_src, W)
+        bwd = gen_backward if ctrl.kind == "G" else disc_backward
+        src_grads = bwd(plan, saved, gout, ctrl.dt, ctrl.cache, need_src, W)
         if W is not None:
             W.flush()
         ctx.saved_net = None

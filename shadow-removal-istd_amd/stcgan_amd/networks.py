@@ -130,8 +130,10 @@ class _HipNet(nn.Module):
         if self._plan is None:
             self._plan = self._make_plan()
         params = self._plan.params
-        ctrl = (self._plan, self.kind, self.training, self.compute_dtype, self._pack_cache, len(sources),
-                self.input_cache, self.grad_consumer, self.stats_only, self.defer_running, batch_stats)
+        ctrl = engine.Ctrl(plan=self._plan, kind=self.kind, train=self.training, dt=self.compute_dtype,
+                           cache=self._pack_cache, nsrc=len(sources), inputs=self.input_cache,
+                           consumer=self.grad_consumer, stats_only=self.stats_only, defer=self.defer_running,
+                           batch_stats=batch_stats)
         return engine.NetFn.apply(ctrl, *sources, *params)
 
     def _batch_stats(self):

@@ -15,6 +15,9 @@
  *                    (Conv/ConvT -> BatchNorm2d pairs, networks.py:104-109,112-121,167-170,176-179)
  *   stc_conv_bwd_bn  input-gradient conv with the consumer BatchNorm-backward reduction fused in
  *   stc_pack_weight / stc_pack_weights  torch weight layout -> GEMM operand layout (one / many tensors)
+ *   stc_upconv_expand / stc_upconv_wgrad_collapse  nn.Upsample(2, nearest) + Conv2d 3x3 s1 p1 up layers (no_conv_t /
+ *                    --NN-upconv, src/models/opt_layers.py:39-56) as the equivalent ConvTranspose2d: the weight map
+ *                    and its adjoint; pack modes STC_PACK_UPCONV_* feed the ConvT kernels from the 3x3 weight
  *   stc_chan_stats / stc_bn_finalize               BatchNorm2d train/eval forward, STCGAN/networks.py:107,109,170,179
  *   stc_bn_bwd_reduce / stc_bn_bwd_apply            BatchNorm2d backward fused with LeakyReLU/ReLU backward
  *                    (with mean == NULL: LeakyReLU(0.2)/ReLU backward alone, networks.py:106,108,158)
@@ -239,9 +242,16 @@ int64_t stc_conv_wgrad_rows_workspace(int B, int IH, int R_out, int Cg);
  *   STC_PACK_CONV_DGRAD  : conv  W[co][ci] -> n=ci, c=co, 4 phases x 4 taps (convT geometry)
  *   STC_PACK_CONV_S1_DGRAD: conv W[co][ci] -> n=ci, c=co, 16 taps
  *   STC_PACK_CONVT_FWD   : convT W[ci][co] -> n=co, c=ci, 4 phases x 4 taps (P=Cin,Q=Cout)
- *   STC_PACK_CONVT_DGRAD : convT W[ci][co] -> n=ci, c=co, 16 taps (conv-s2 geometry)      */
+ *   STC_PACK_CONVT_DGRAD : convT W[ci][co] -> n=ci, c=co, 16 taps (conv-s2 geometry)
+ * Resize-convolution up layers, nn.Upsample(2, "nearest") + nn.Conv2d(3, 1, 1) with zero padding
+ * (src/models/opt_layers.py:39-56): W is the conv weight [Co][Ci][3][3] fp32, P = Ci, Q = Co as for the ConvT
+ * modes, and out is byte for byte what the ConvT mode makes from the equivalent ConvT weight
+ * W4 = stc_upconv_expand(W) (below), which is never materialised; one bf16 rounding, after the fp32 sums.
+ *   STC_PACK_UPCONV_FWD  : as STC_PACK_CONVT_FWD of W4      STC_PACK_UPCONV_DGRAD: as STC_PACK_CONVT_DGRAD of W4
+ * These two validate before the launch: P, Q, N_pad, C_pad > 0, the padded extents cover the channels, W and out
+ * non-null.                                                                                   */
 enum { STC_PACK_CONV_FWD = 0, STC_PACK_CONV_DGRAD = 1, STC_PACK_CONV_S1_DGRAD = 2,
-       STC_PACK_CONVT_FWD = 3, STC_PACK_CONVT_DGRAD = 4 };
+       STC_PACK_CONVT_FWD = 3, STC_PACK_CONVT_DGRAD = 4, STC_PACK_UPCONV_FWD = 5, STC_PACK_UPCONV_DGRAD = 6 };
 int stc_pack_weight(int dtype, int mode, const float* W, int P, int Q,
                     void* out, int N_pad, int C_pad, void* stream);
 /* Multi-tensor packing: all stale packed operands of a network after an optimiser step in one
@@ -255,6 +265,18 @@ typedef struct {
   void* out;
 } stc_pack_desc;
 int stc_pack_weights(int dtype, int n, const stc_pack_desc* descs, void* stream);
+/* The ConvTranspose2d(4, 2, 1) weight W4[Ci][Co][4][4] equivalent to the resize-convolution weight
+ * w3[Co][Ci][3][3] (src/models/opt_layers.py:39-56; nearest 2x upsampling + zero-padded 3x3 conv):
+ *   W4[ci][co][k][l] = sum_{a in rows(k)} sum_{b in rows(l)} w3[co][ci][a][b],
+ *   rows(0) = {2}, rows(1) = {1, 2}, rows(2) = {0, 1}, rows(3) = {0}
+ * in fp32, a ascending outside, b ascending inside, summed left to right (adds only: reproducible bit for bit).
+ * Ci, Co > 0, non-null pointers (checked before the launch).                                   */
+int stc_upconv_expand(const float* w3, int Ci, int Co, float* W4, void* stream);
+/* Its adjoint (src/models/opt_layers.py:39-56): the conv weight gradient from the ConvT-layout one,
+ *   dw3[co][ci][a][b] = sum_{k : a in rows(k)} sum_{l : b in rows(l)} dW4[ci][co][k][l]
+ * (a = 0: k in {2, 3}, a = 1: {1, 2}, a = 2: {0, 1}), fp32, k ascending outside, l ascending inside.  dw3 needs
+ * 4-byte alignment only (a slice of a flat gradient buffer).                                    */
+int stc_upconv_wgrad_collapse(const float* dW4, int Ci, int Co, float* dw3, void* stream);
 
 /* ---- batch norm -------------------------------------------------------------
  * stc_chan_stats: per-channel partial statistics of x over pixel chunks:

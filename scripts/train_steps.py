@@ -31,6 +31,10 @@ ap.add_argument("--use-dropout", type=int, default=0, help="1: generators with u
 ap.add_argument("--droprate", type=float, default=0.5)
 ap.add_argument("--ab-dropout", action="store_true", help="a second trainer with use_dropout=True; the two are "
                 "timed alternately, one per repeat (same process)")
+ap.add_argument("--nn-upconv", type=int, default=0, help="1: generators with Upsample + Conv2d(3) up layers "
+                "(args.NN_upconv)")
+ap.add_argument("--ab-upconv", action="store_true", help="a second trainer with NN_upconv=True; the two are timed "
+                "alternately, one per repeat (same process)")
 args = ap.parse_args()
 engine.WGRAD_OVERLAP = args.wgrad_overlap > 0
 if args.wgrad_overlap > 1:
@@ -39,13 +43,15 @@ a = types.SimpleNamespace(devices=["cuda:0"], tasks=["train"], lr_G=5e-5, lr_D=2
                           D_loss_fn="standard", D_loss_type="normal", ngf=64, dtype=args.dtype, load_weights_g1=None,
                           load_weights_g2=None, load_weights_d1=None, load_weights_d2=None,
                           streams=bool(args.streams), fused_objectives=bool(args.fused),
-                          use_dropout=bool(args.use_dropout), droprate=args.droprate)
+                          use_dropout=bool(args.use_dropout), droprate=args.droprate, NN_upconv=bool(args.nn_upconv))
 torch.manual_seed(1234)
 tr = STCGAN(a)
 drop_trs = None
 if args.ab_dropout:
     a_d = types.SimpleNamespace(**{**vars(a), "use_dropout": True})
     drop_trs = [tr, STCGAN(a_d)]
+elif args.ab_upconv:
+    drop_trs = [tr, STCGAN(types.SimpleNamespace(**{**vars(a), "NN_upconv": True}))]
 import stcgan_amd.stcgan as _st  # noqa: E402
 
 
@@ -58,7 +64,7 @@ def _slowed(step):
     return _slow
 
 
-for t_ in drop_trs or [tr]:  # (every trainer: --ab-dropout switches between two)
+for t_ in drop_trs or [tr]:  # (every trainer: --ab-dropout / --ab-upconv switch between two)
     t_.set_early = lambda v: setattr(_st, "EARLY_D_BACKWARD", int(v))  # (--ab-attr early=0,1,2)
     t_.set_late = lambda v: setattr(_st, "LATE_STATS_CALLS", bool(v))  # (--ab-attr late=0,1)
     if args.host_sleep_us:
@@ -74,7 +80,7 @@ torch.cuda.synchronize()
 ab = [int(v) for v in args.ab.split(",")] if args.ab else None
 plans = json.loads(args.ab_plans) if args.ab_plans else None
 res = {}
-drop_label = f"use_dropout={args.use_dropout}"
+drop_label = f"use_dropout={args.use_dropout}" + (f", NN_upconv={args.nn_upconv}" if args.nn_upconv else "")
 attr = None
 if args.ab_attr:
     an, av = args.ab_attr.split("=")
@@ -82,7 +88,7 @@ if args.ab_attr:
 for rep in range(args.repeat):
     if drop_trs:
         tr = drop_trs[rep % 2]
-        drop_label = f"use_dropout={rep % 2}"
+        drop_label = f"NN_upconv={rep % 2}" if args.ab_upconv else f"use_dropout={rep % 2}"
         for _ in range(2):
             tr.train_step(x, m, y)
         torch.cuda.synchronize()

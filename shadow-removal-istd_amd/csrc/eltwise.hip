@@ -614,30 +614,280 @@ __global__ void pack_multi_kernel(const PackSet ps) {
   }
 }
 
+// ------------------------------------------------------------------ resize-convolution weights
+// nn.Upsample(2, "nearest") + nn.Conv2d(3, 1, 1, zero padding) (src/models/opt_layers.py:39-56) is the
+// ConvTranspose2d(4, 2, 1) whose weight is W4[ci][co][k][l] = sum_{a in rows(k)} sum_{b in rows(l)} w3[co][ci][a][b],
+// rows(0) = {2}, rows(1) = {1, 2}, rows(2) = {0, 1}, rows(3) = {0}.  The kernels below apply that map (and its
+// adjoint) between the conv layout [Co][Ci][3][3] and the ConvT layout [Ci][Co][4][4] / its packed operands.
+// The two sides differ by the (ci, co) transpose, so a block moves a 16 x 16 (ci, co) tile through LDS: the
+// w3 side is accessed as 16 runs of 16 * 9 contiguous floats (one per co), the W4 side with the tile's other
+// index fastest.  The LDS tile is [co][ci * 9 + tap] with a row pitch chosen by which index the lanes of
+// the compute phase walk (ds b32 accesses: 32 banks, conflicts within a 32-lane half):
+//   ci fastest (16 ci x 2 co per half): bank = 9 ci + pitch * co; 9 ci takes 16 distinct residues, 9 ci + 16 the
+//     other 16 -> pitch = 144 (= 16 mod 32) is conflict-free;
+//   co fastest (16 co x 2 ci per half): bank = pitch * co + 9 ci; pitch = 146 (= 18 mod 32) puts the 16 co on the
+//     16 even banks and the second ci (+ 9) on the odd ones.
+// The coalesced side walks a row linearly (consecutive lanes, consecutive banks; the 2-float gap of pitch 146
+// costs a 2-way conflict only in a half that straddles two rows).
+// Fixed summation order, fp32 adds only (nothing here can contract into an FMA): a ascending outside, b
+// ascending inside, left to right, starting from the first term; the adjoint: k outside, l inside.
+constexpr int UPC_PITCH_CI = 144, UPC_PITCH_CO = 146;
+
+__device__ __forceinline__ int upc_lo(int k) { return k == 0 ? 2 : (k == 1 ? 1 : 0); }
+__device__ __forceinline__ int upc_hi(int k) { return k <= 1 ? 2 : (k == 2 ? 1 : 0); }
+
+// the 16 taps of W4 from the 9 of w3
+__device__ __forceinline__ void upc_expand16(const float* w3, float* w4) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+      float acc = w3[upc_lo(k) * 3 + upc_lo(l)];
+#pragma unroll
+      for (int a = upc_lo(k); a <= upc_hi(k); ++a)
+#pragma unroll
+        for (int b = upc_lo(l); b <= upc_hi(l); ++b)
+          if (a != upc_lo(k) || b != upc_lo(l)) acc = acc + w3[a * 3 + b];
+      w4[k * 4 + l] = acc;
+    }
+}
+
+// the adjoint: tap a of w3 collects k in {2, 3} (a = 0), {1, 2} (a = 1), {0, 1} (a = 2)
+__device__ __forceinline__ void upc_collapse9(const float* w4, float* w3) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const int k0 = 2 - a, l0 = 2 - b;
+      w3[a * 3 + b] = ((w4[k0 * 4 + l0] + w4[k0 * 4 + l0 + 1]) + w4[(k0 + 1) * 4 + l0]) + w4[(k0 + 1) * 4 + l0 + 1];
+    }
+}
+
+// w3 tile (ci0.., co0..) -> LDS [16][pitch], zeros outside Ci x Co (the operands' channel padding)
+__device__ __forceinline__ void upc_load_tile(const float* w3, int Ci, int Co, int ci0, int co0, int pitch, float* s) {
+  const int run = 9 * max(0, min(16, Ci - ci0));  // floats of one co row that exist
+  for (int idx = threadIdx.x; idx < 16 * 144; idx += 256) {
+    const int col = idx / 144, r = idx - col * 144;
+    float v = 0.f;
+    if (co0 + col < Co && r < run) v = w3[((long long)(co0 + col) * Ci + ci0) * 9 + r];
+    s[col * pitch + r] = v;
+  }
+}
+
+// One 16 x 16 tile of a packed ConvT operand (pack_kernel's layouts for the modes CONVT_FWD / CONVT_DGRAD) from w3;
+// the tiles cover N_pad x C_pad, so the padding is written (zeros), as pack_kernel does.
+template <typename T>
+__device__ __forceinline__ void upc_pack_tile(int mode, const float* w3, int Ci, int Co, T* out, int N_pad, int C_pad,
+                                              int tile, float* s) {
+  const bool fwd = mode == STC_PACK_UPCONV_FWD;  // n = co, c = ci, 4 phases x 4 taps; else n = ci, c = co, 16 taps
+  const int ct = (C_pad + 15) / 16;
+  const int n0 = (tile / ct) * 16, c0 = (tile % ct) * 16;
+  const int ci0 = fwd ? c0 : n0, co0 = fwd ? n0 : c0;
+  const int pitch = fwd ? UPC_PITCH_CI : UPC_PITCH_CO;
+  __syncthreads();  // (the previous tile's readers)
+  upc_load_tile(w3, Ci, Co, ci0, co0, pitch, s);
+  __syncthreads();
+  const int cl = threadIdx.x & 15, nl = threadIdx.x >> 4;  // consecutive lanes, consecutive c
+  const int n = n0 + nl, c = c0 + cl;
+  if (n >= N_pad || c >= C_pad) return;
+  const float* src = fwd ? s + nl * pitch + cl * 9 : s + cl * pitch + nl * 9;
+  float w3r[9], w[16];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) w3r[t] = src[t];
+  upc_expand16(w3r, w);
+  if (!fwd) {
+#pragma unroll
+    for (int t = 0; t < 16; ++t) st1<T>(out + ((long long)n * 16 + t) * C_pad + c, w[t]);
+  } else {
+#pragma unroll
+    for (int z = 0; z < 4; ++z) {
+      const int ph = z >> 1, pw = z & 1;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int kh = (1 - ph) + 2 * (t >> 1), kw = (1 - pw) + 2 * (t & 1);
+        st1<T>(out + (((long long)z * N_pad + n) * 4 + t) * C_pad + c, w[kh * 4 + kw]);
+      }
+    }
+  }
+}
+
+static inline long long upc_tiles(int a, int b) { return (long long)((a + 15) / 16) * ((b + 15) / 16); }
+
+template <typename T>
+__global__ void __launch_bounds__(256) upconv_pack_kernel(int mode, const float* w3, int Ci, int Co, T* out, int N_pad,
+                                                          int C_pad, int ntiles) {
+  __shared__ float s[16 * UPC_PITCH_CO];
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x)  // (block-uniform)
+    upc_pack_tile<T>(mode, w3, Ci, Co, out, N_pad, C_pad, tile, s);
+}
+
+// the multi-tensor form: the UPCONV descriptors of a PackSet (bstart: their block ranges)
+template <typename T>
+__global__ void __launch_bounds__(256) upconv_pack_multi_kernel(const PackSet ps) {
+  __shared__ float s[16 * UPC_PITCH_CO];
+  int i = 0;
+  while (i + 1 < ps.n && (int)blockIdx.x >= ps.bstart[i + 1]) ++i;
+  const stc_pack_desc& d = ps.d[i];
+  const int nblk = ps.bstart[i + 1] - ps.bstart[i];
+  const int ntiles = (int)(((d.N_pad + 15) / 16) * ((d.C_pad + 15) / 16));
+  for (int tile = blockIdx.x - ps.bstart[i]; tile < ntiles; tile += nblk)
+    upc_pack_tile<T>(d.mode, d.W, d.P, d.Q, reinterpret_cast<T*>(d.out), d.N_pad, d.C_pad, tile, s);
+}
+
+// W4[ci][co][4][4] fp32 from w3: lane (co fastest) writes its 16 taps, 16 lanes one 1 KiB run
+__global__ void __launch_bounds__(256) upconv_expand_kernel(const float* w3, int Ci, int Co, float* W4, int ntiles,
+                                                            int vec) {
+  __shared__ float s[16 * UPC_PITCH_CO];
+  const int cot = (Co + 15) / 16;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int ci0 = (tile / cot) * 16, co0 = (tile % cot) * 16;
+    __syncthreads();
+    upc_load_tile(w3, Ci, Co, ci0, co0, UPC_PITCH_CO, s);
+    __syncthreads();
+    const int col = threadIdx.x & 15, cil = threadIdx.x >> 4;
+    const int ci = ci0 + cil, co = co0 + col;
+    if (ci >= Ci || co >= Co) continue;
+    float w3r[9], w[16];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) w3r[t] = s[col * UPC_PITCH_CO + cil * 9 + t];
+    upc_expand16(w3r, w);
+    float* dst = W4 + ((long long)ci * Co + co) * 16;
+    if (vec) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+        reinterpret_cast<float4*>(dst)[v] = make_float4(w[4 * v], w[4 * v + 1], w[4 * v + 2], w[4 * v + 3]);
+    } else {
+#pragma unroll
+      for (int t = 0; t < 16; ++t) dst[t] = w[t];
+    }
+  }
+}
+
+// dw3[co][ci][3][3] from dW4[ci][co][4][4]: lane (co fastest) reads its 16 taps and leaves its 9 sums in the LDS
+// tile, which the block then writes out as 16 runs of 16 * 9 contiguous floats (4-byte stores: dw3 may be any
+// slice of a flat gradient buffer)
+__global__ void __launch_bounds__(256) upconv_collapse_kernel(const float* dW4, int Ci, int Co, float* dw3, int ntiles,
+                                                              int vec) {
+  __shared__ float s[16 * UPC_PITCH_CO];
+  const int cot = (Co + 15) / 16;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int ci0 = (tile / cot) * 16, co0 = (tile % cot) * 16;
+    const int col = threadIdx.x & 15, cil = threadIdx.x >> 4;
+    const int ci = ci0 + cil, co = co0 + col;
+    __syncthreads();
+    if (ci < Ci && co < Co) {
+      const float* src = dW4 + ((long long)ci * Co + co) * 16;
+      float w[16], w3r[9];
+      if (vec) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const float4 f = reinterpret_cast<const float4*>(src)[v];
+          w[4 * v] = f.x; w[4 * v + 1] = f.y; w[4 * v + 2] = f.z; w[4 * v + 3] = f.w;
+        }
+      } else {
+#pragma unroll
+        for (int t = 0; t < 16; ++t) w[t] = src[t];
+      }
+      upc_collapse9(w, w3r);
+#pragma unroll
+      for (int t = 0; t < 9; ++t) s[col * UPC_PITCH_CO + cil * 9 + t] = w3r[t];
+    }
+    __syncthreads();
+    const int run = 9 * min(16, Ci - ci0);
+    for (int idx = threadIdx.x; idx < 16 * 144; idx += 256) {
+      const int c2 = idx / 144, r = idx - c2 * 144;
+      if (co0 + c2 < Co && r < run) dw3[((long long)(co0 + c2) * Ci + ci0) * 9 + r] = s[c2 * UPC_PITCH_CO + r];
+    }
+  }
+}
+
+static inline bool upc_mode(int mode) { return mode == STC_PACK_UPCONV_FWD || mode == STC_PACK_UPCONV_DGRAD; }
+
 extern "C" int stc_pack_weights(int dtype, int n, const stc_pack_desc* descs, void* stream) {
   STC_REQUIRE(n >= 0 && n <= STC_PACK_MAX && (n == 0 || descs), "stc_pack_weights: bad count %d", n);
   if (n == 0) return 0;
-  PackSet ps{};
-  ps.n = n;
-  int b = 0;
+  // the 4x4 descriptors go to pack_multi_kernel, the resize-convolution ones to upconv_pack_multi_kernel (a call
+  // of one kind is one launch)
+  PackSet ps{}, us{};
+  int b = 0, ub = 0;
   for (int i = 0; i < n; ++i) {
-    STC_REQUIRE(descs[i].mode >= 0 && descs[i].mode <= 4 && descs[i].W && descs[i].out, "stc_pack_weights: bad desc %d", i);
-    ps.d[i] = descs[i];
-    ps.bstart[i] = b;
+    STC_REQUIRE(descs[i].mode >= 0 && descs[i].mode <= 6 && descs[i].W && descs[i].out, "stc_pack_weights: bad desc %d", i);
+    if (upc_mode(descs[i].mode)) {
+      const stc_pack_desc& d = descs[i];
+      STC_REQUIRE(d.P > 0 && d.Q > 0 && d.N_pad > 0 && d.C_pad > 0, "stc_pack_weights: bad desc %d (channels)", i);
+      STC_REQUIRE(d.N_pad >= (d.mode == STC_PACK_UPCONV_FWD ? d.Q : d.P) &&
+                  d.C_pad >= (d.mode == STC_PACK_UPCONV_FWD ? d.P : d.Q), "stc_pack_weights: bad desc %d (padding)", i);
+      us.d[us.n] = d;
+      us.bstart[us.n++] = ub;
+      ub += (int)std::min<long long>(upc_tiles(d.N_pad, d.C_pad), 1024);
+      continue;
+    }
+    ps.d[ps.n] = descs[i];
+    ps.bstart[ps.n++] = b;
     const long long total = (long long)descs[i].N_pad * descs[i].C_pad;
     b += (int)std::max<long long>(1, std::min<long long>((total + 255) / 256, 1024));
   }
-  ps.bstart[n] = b;
+  ps.bstart[ps.n] = b;
+  us.bstart[us.n] = ub;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == STC_F32) hipLaunchKernelGGL(pack_multi_kernel<float>, dim3(b), dim3(256), 0, st, ps);
-  else hipLaunchKernelGGL(pack_multi_kernel<bf16>, dim3(b), dim3(256), 0, st, ps);
+  if (ps.n) {
+    if (dtype == STC_F32) hipLaunchKernelGGL(pack_multi_kernel<float>, dim3(b), dim3(256), 0, st, ps);
+    else hipLaunchKernelGGL(pack_multi_kernel<bf16>, dim3(b), dim3(256), 0, st, ps);
+    STC_CHECK_LAUNCH();
+  }
+  if (us.n) {
+    if (dtype == STC_F32) hipLaunchKernelGGL(upconv_pack_multi_kernel<float>, dim3(ub), dim3(256), 0, st, us);
+    else hipLaunchKernelGGL(upconv_pack_multi_kernel<bf16>, dim3(ub), dim3(256), 0, st, us);
+    STC_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+extern "C" int stc_upconv_expand(const float* w3, int Ci, int Co, float* W4, void* stream) {
+  STC_REQUIRE(Ci > 0 && Co > 0, "stc_upconv_expand: channels %d x %d", Ci, Co);
+  STC_REQUIRE(w3 && W4, "stc_upconv_expand: null pointer");
+  const long long nt = upc_tiles(Ci, Co);
+  STC_REQUIRE(nt < (1ll << 31), "stc_upconv_expand: too many channels");
+  const int vec = ((uintptr_t)W4 & 15) == 0;
+  hipLaunchKernelGGL(upconv_expand_kernel, dim3((int)std::min<long long>(nt, 4096)), dim3(256), 0, (hipStream_t)stream,
+                     w3, Ci, Co, W4, (int)nt, vec);
+  STC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stc_upconv_wgrad_collapse(const float* dW4, int Ci, int Co, float* dw3, void* stream) {
+  STC_REQUIRE(Ci > 0 && Co > 0, "stc_upconv_wgrad_collapse: channels %d x %d", Ci, Co);
+  STC_REQUIRE(dW4 && dw3, "stc_upconv_wgrad_collapse: null pointer");
+  const long long nt = upc_tiles(Ci, Co);
+  STC_REQUIRE(nt < (1ll << 31), "stc_upconv_wgrad_collapse: too many channels");
+  const int vec = ((uintptr_t)dW4 & 15) == 0;
+  hipLaunchKernelGGL(upconv_collapse_kernel, dim3((int)std::min<long long>(nt, 4096)), dim3(256), 0,
+                     (hipStream_t)stream, dW4, Ci, Co, dw3, (int)nt, vec);
   STC_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int stc_pack_weight(int dtype, int mode, const float* W, int P, int Q, void* out, int N_pad, int C_pad,
                                void* stream) {
-  STC_REQUIRE(mode >= 0 && mode <= 4, "stc_pack_weight: bad mode");
+  STC_REQUIRE(mode >= 0 && mode <= 6, "stc_pack_weight: bad mode");
+  if (upc_mode(mode)) {
+    STC_REQUIRE(P > 0 && Q > 0 && N_pad > 0 && C_pad > 0, "stc_pack_weight: channels %d x %d -> %d x %d", P, Q, N_pad,
+                C_pad);
+    STC_REQUIRE(W && out, "stc_pack_weight: null pointer");
+    STC_REQUIRE(N_pad >= (mode == STC_PACK_UPCONV_FWD ? Q : P) && C_pad >= (mode == STC_PACK_UPCONV_FWD ? P : Q),
+                "stc_pack_weight: padded extent below the channel count");
+    const long long nt = upc_tiles(N_pad, C_pad);
+    STC_REQUIRE(nt < (1ll << 31), "stc_pack_weight: too many channels");
+    const int blocks = (int)std::min<long long>(nt, 4096);
+    if (dtype == STC_F32)
+      hipLaunchKernelGGL(upconv_pack_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, mode, W, P, Q,
+                         (float*)out, N_pad, C_pad, (int)nt);
+    else
+      hipLaunchKernelGGL(upconv_pack_kernel<bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, mode, W, P, Q,
+                         (bf16*)out, N_pad, C_pad, (int)nt);
+    STC_CHECK_LAUNCH();
+    return 0;
+  }
   const bool phased = mode == STC_PACK_CONV_DGRAD || mode == STC_PACK_CONVT_FWD;
   const int nph = phased ? 4 : 1, taps = phased ? 4 : 16;
   hipStream_t st = (hipStream_t)stream;

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("STC_LIB_PATH") or os.path.join(_HERE, "libstcgan_hip.
 F32, BF16 = 0, 1
 CONV_S2, CONV_S1, CONVT_S2, CONV_S1_DGRAD = 0, 1, 2, 3
 PACK_CONV_FWD, PACK_CONV_DGRAD, PACK_CONV_S1_DGRAD, PACK_CONVT_FWD, PACK_CONVT_DGRAD = 0, 1, 2, 3, 4
+PACK_UPCONV_FWD, PACK_UPCONV_DGRAD = 5, 6  # the ConvT operands from an Upsample + Conv2d(3, 1, 1) weight
 LOSS_L1, LOSS_MSE_CONST, LOSS_BCE_CONST = 0, 1, 2
 LOSS_COMBINE_D, LOSS_COMBINE_G = 0, 1
 
@@ -95,6 +96,8 @@ _SIGS = {
     "stc_conv_wgrad_query": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "stc_pack_weight": (_i32, [_i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
     "stc_pack_weights": (_i32, [_i32, _i32, _vp, _vp]),
+    "stc_upconv_expand": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "stc_upconv_wgrad_collapse": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "stc_chan_stats": (_i32, [_i32, _i32, View, _i32, _vp, _i32, _vp]),
     "stc_chan_stats_chunks": (_i32, [_i32, _i32, _i32]),
     "stc_chan_sum": (_i32, [_i32, _i32, View, _i32, _i32, _vp, _i32, _vp, _vp]),

@@ -228,21 +228,27 @@ class GenPlan:
         self.net = net
         outer = net.model  # outermost UnetSkipConnectionBlock
         self.in_c = outer.model[0].in_channels
-        self.out_c = outer.model[3].out_channels
         conv, bnd, convT, bnu, drop = [], {}, {}, {}, {}
+        names = {id(m): n for n, m in net.named_modules()}
+        kinds = {}  # {level: the up layer is a resize-convolution}
+
+        def up(k, m):
+            convT[k], kinds[k] = _up_layer(m, names.get(id(m), "?"))
+
         conv.append(outer.model[0])
-        convT[0] = outer.model[3]
+        up(0, outer.model[3])
+        self.out_c = convT[0].out_channels
         blk = outer.model[1]
         k = 1
         while True:
             seq = blk.model
             conv.append(seq[1])
             if blk.innermost:
-                convT[k] = seq[3]
+                up(k, seq[3])
                 bnu[k] = seq[4]
                 break
             bnd[k] = seq[2]
-            convT[k] = seq[5]
+            up(k, seq[5])
             bnu[k] = seq[6]
             if isinstance(seq[-1], torch.nn.Dropout):  # use_dropout: after the up-norm (networks.py)
                 p = seq[-1].p
@@ -253,6 +259,16 @@ class GenPlan:
             blk = seq[3]
             k += 1
         self.L = len(conv)
+        # up layers: nn.ConvTranspose2d(4, 2, 1) (weight [Ci][Co][4][4]), or -- every one of them, no_conv_t -- the
+        # nn.Conv2d(3, 1, 1) of an Upsample + Conv2d pair (weight [Co][Ci][3][3]), run as the ConvT it equals
+        if len(set(kinds.values())) > 1:
+            raise NotImplementedError(
+                "stcgan_amd: a generator mixing ConvTranspose2d and Upsample + Conv2d up layers is not supported -- "
+                "resize-convolution: " + ", ".join(names.get(id(convT[j]), "?") for j in sorted(kinds) if kinds[j])
+                + "; ConvTranspose2d: " + ", ".join(names.get(id(convT[j]), "?") for j in sorted(kinds) if not kinds[j]))
+        self.upconv = kinds[0]
+        self.pack_t_fwd = L.PACK_UPCONV_FWD if self.upconv else L.PACK_CONVT_FWD
+        self.pack_t_dgrad = L.PACK_UPCONV_DGRAD if self.upconv else L.PACK_CONVT_DGRAD
         self.conv, self.bnd, self.convT, self.bnu = conv, bnd, convT, bnu
         # {level k: p}: train-mode dropout on the output of BN_up[k] (the blocks right above the innermost one)
         self.drop = drop
@@ -260,6 +276,33 @@ class GenPlan:
         # which norm the network uses: BatchNorm2d, or InstanceNorm2d (affine or not)
         self.inorm, self.affine = _norm_kind(list(bnd.values()) + list(bnu.values()))
         self.params = list(net.parameters())
+
+
+def _up_layer(m, name):
+    """(the module that holds an up layer's weight and bias, is it a resize-convolution): m is the reference's
+    nn.ConvTranspose2d, or nn.Sequential(nn.Upsample(2, "nearest"), nn.Conv2d(3, 1, 1, padding_mode="zeros")), which
+    the ConvT kernels run; any other form of the pair raises NotImplementedError."""
+    nn = torch.nn
+    if isinstance(m, nn.ConvTranspose2d):
+        return m, False
+    if not (isinstance(m, nn.Sequential) and len(m) == 2 and isinstance(m[0], nn.Upsample)
+            and isinstance(m[1], nn.Conv2d)):
+        raise NotImplementedError(f"stcgan_amd: up layer {name} ({type(m).__name__}) is neither a ConvTranspose2d nor "
+                                  "nn.Sequential(nn.Upsample, nn.Conv2d)")
+    u, c = m
+    sf = u.scale_factor
+    sf = tuple(sf) if isinstance(sf, (tuple, list)) else (sf, sf)
+    if u.mode != "nearest" or u.size is not None or sf != (2, 2):
+        raise NotImplementedError(f"stcgan_amd: up layer {name}: nn.Upsample(scale_factor=2, mode='nearest') only, got "
+                                  f"scale_factor={u.scale_factor!r}, size={u.size!r}, mode={u.mode!r}")
+    if c.padding_mode != "zeros":
+        raise NotImplementedError(f"stcgan_amd: up layer {name}: padding_mode={c.padding_mode!r} is not supported "
+                                  "(the conv kernels' halo is zero-filled: padding_mode='zeros' only)")
+    if (tuple(c.kernel_size), tuple(c.stride), c.padding, tuple(c.dilation), c.groups) != \
+            ((3, 3), (1, 1), (1, 1), (1, 1), 1):
+        raise NotImplementedError(f"stcgan_amd: up layer {name}: nn.Conv2d(kernel_size=3, stride=1, padding=1) only, "
+                                  f"got {c}")
+    return c, True
 
 
 def _sizes(H, W, Lv):
@@ -464,7 +507,7 @@ def gen_forward(plan, sources, train, dt, cache, save, batch_stats=None):
             ops.bn_apply(B, rv, co[k], dt, None, L.nhwc_view(cr[k]), 0.0)
     # ---- up path
     for k in range(Lv - 1, 0, -1):
-        wt = ops.packed(cache, plan.convT[k].weight, L.PACK_CONVT_FWD, co[k - 1], cin_t(k), dt)
+        wt = ops.packed(cache, plan.convT[k].weight, plan.pack_t_fwd, co[k - 1], cin_t(k), dt)
         # statistics over the full ConvT extent (before the crop of an odd level)
         t, st_u[k] = _conv_norm_act(L.CONVT_S2, B, L.nhwc_view(cr[k]), cin_t(k), wt, co[k - 1], L.nhwc_view(rq[k]), dt,
                                     plan.bnu[k], mode, L.nhwc_view(rq[k], 0, *S[k]),
@@ -474,7 +517,7 @@ def gen_forward(plan, sources, train, dt, cache, save, batch_stats=None):
     # ---- outermost: tanh(convT_0(cr[0]) + bias) -> NCHW fp32
     Ho, Wo = 2 * S[1][0], 2 * S[1][1]
     y = torch.empty((B, plan.out_c, Ho, Wo), dtype=torch.float32, device=dev)
-    wt0 = ops.packed(cache, plan.convT[0].weight, L.PACK_CONVT_FWD, plan.out_c, 2 * co[0], dt)
+    wt0 = ops.packed(cache, plan.convT[0].weight, plan.pack_t_fwd, plan.out_c, 2 * co[0], dt)
     ops.conv(L.CONVT_S2, B, L.nhwc_view(cr[0]), 2 * co[0], wt0, plan.out_c, L.nchw_view(y), dt,
              bias=plan.convT[0].bias, tanh=True, out_f32=True)
     saved = None
@@ -521,9 +564,16 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
         wT = plan.convT[k].weight
         if need_w:  # D = convT input (grid S[k+1]), G = dq gathered at stride 2
             out = W.dest(wT)
-            lane.run(lambda: ops.wgrad(B, 2, L.nhwc_view(cr[k]), cin_t, dqv, cg, cout_t, dt, device=dev, out=out), dq,
-                     pixels=S[k + 1][0] * S[k + 1][1])
-        wd = ops.packed(cache, wT, L.PACK_CONVT_DGRAD, cin_t, cg, dt)
+            if plan.upconv:
+                def wg():  # (run at once, by lane.run: the scratch, the GEMM and the collapse on its stream)
+                    dW4 = torch.empty((cin_t, cout_t, 4, 4), dtype=torch.float32, device=dev)
+                    ops.wgrad(B, 2, L.nhwc_view(cr[k]), cin_t, dqv, cg, cout_t, dt, device=dev, out=dW4)
+                    ops.upconv_wgrad_collapse(dW4, out)
+                lane.run(wg, dq, pixels=S[k + 1][0] * S[k + 1][1])
+            else:
+                lane.run(lambda: ops.wgrad(B, 2, L.nhwc_view(cr[k]), cin_t, dqv, cg, cout_t, dt, device=dev, out=out),
+                         dq, pixels=S[k + 1][0] * S[k + 1][1])
+        wd = ops.packed(cache, wT, plan.pack_t_dgrad, cin_t, cg, dt)
         if k == Lv - 1:
             gcat[k] = _nhwc(B, *S[Lv], cin_t, dt, dev)
             _trace("G", ("gcat", k), gcat[k])

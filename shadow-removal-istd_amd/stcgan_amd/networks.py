@@ -17,6 +17,14 @@ src/models/stcgan_g.py:120-132 (the STCGAN/networks.py version raises there);
 forward also accepts a list/tuple of NCHW tensors, treated as their channel
 concatenation without materialising it (what ``torch.cat(..., 1)`` would give).
 
+``no_conv_t=True`` (the ``--NN-upconv`` option of the reference's src/ line, src/models/opt_layers.py:39-56): every
+``ConvTranspose2d(4, 2, 1)`` of the up path becomes ``nn.Upsample(scale_factor=2, mode="nearest")`` +
+``nn.Conv2d(3, 1, 1)`` (resize-convolution, no checkerboard artifacts).  The same HIP kernels run it: with zero
+padding the pair is exactly a ConvTranspose2d whose 4x4 weight is a fixed sum of the 3x3 taps.
+``padding_mode`` is ``"zeros"``; the reference's helper uses ``"reflect"`` (equal to replicate padding of the
+low-resolution input by one pixel), which the zero-filling halo loaders cannot express: out of scope, refused.
+``conv_t_state_dict()`` exports such a generator as the plain ST-CGAN one.
+
 Modes are torch's, read from the modules at every call: the network's own ``training`` flag governs the dropout
 levels, its BatchNorm2d children's flags govern batch statistics + running update (train) against running statistics
 with untouched buffers (eval) -- ``net.eval()``, or ``net.train()`` with the norm children in eval (``freeze_norm``).
@@ -81,6 +89,26 @@ def check_norm_layer(norm_layer, use_dropout=False):
         raise NotImplementedError("stcgan_amd: use_dropout=True together with nn.InstanceNorm2d is not supported "
                                   "(the dropout kernels are written against the BatchNorm per-channel tables)")
     return "instance"
+
+
+def check_flag(name, v):
+    """A boolean option as a bool (True / False / 0 / 1; ValueError otherwise)."""
+    if not isinstance(v, (bool, int)) or v not in (0, 1):
+        raise ValueError(f"stcgan_amd: {name} must be a bool, got {v!r}")
+    return bool(v)
+
+
+def upconv_to_conv_t(weight):
+    """The ``ConvTranspose2d(4, 2, 1)`` weight [cin, cout, 4, 4] that computes what ``nn.Upsample(2, "nearest")`` +
+    ``nn.Conv2d(cin, cout, 3, 1, 1)`` with this weight [cout, cin, 3, 3] computes (zero padding; fp32, on the weight's
+    ROCm device: stc_upconv_expand).  W4[ci][co][k][l] = sum of w[co][ci][a][b] over a in rows(k), b in rows(l), with
+    rows(0) = {2}, rows(1) = {1, 2}, rows(2) = {0, 1}, rows(3) = {0}."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError(f"stcgan_amd: a [cout, cin, 3, 3] conv weight is expected, got {tuple(weight.shape)}")
+    if not weight.is_cuda:
+        raise RuntimeError("stcgan_amd: upconv_to_conv_t runs on the GPU only (HIP kernel); move the weight to a "
+                           "ROCm device")
+    return ops.upconv_expand(weight.detach().float())
 
 
 class _HipNet(nn.Module):
@@ -182,8 +210,13 @@ class UnetGenerator(_HipNet):
     kind = "G"
 
     def __init__(self, in_channels, out_channels, ngf=64, num_downs=8, norm_layer=nn.BatchNorm2d,
-                 use_dropout=False, drop_rate=None):
-        """use_dropout: nn.Dropout after the up-norm of the num_downs - 5 blocks above the innermost one, as the
+                 use_dropout=False, drop_rate=None, no_conv_t=False):
+        """no_conv_t (the reference's keyword, src/models/opt_layers.py:39-56): each up layer is
+        nn.Sequential(nn.Upsample(scale_factor=2, mode="nearest"), nn.Conv2d(cin, cout, 3, 1, 1)) at the ConvTranspose2d's
+        index, its keys ``...model.N.1.weight`` [cout, cin, 3, 3] (and ``model.3.1.bias`` on the outermost layer).
+        padding_mode is "zeros": the reference helper's "reflect" (a replicate halo of the low-resolution input) is
+        out of scope, the halo loaders zero-fill.  Composes with every other option.
+        use_dropout: nn.Dropout after the up-norm of the num_downs - 5 blocks above the innermost one, as the
         reference (p = 0.5; ``drop_rate`` overrides it, 0 <= drop_rate < 1).  Train mode only; the masks are a
         counter-based function of this generator's {seed, offset} (set_dropout_seed / dropout_state).  p is read
         from the nn.Dropout modules when the launch plan is made (the first forward, and again after a module move):
@@ -192,19 +225,43 @@ class UnetGenerator(_HipNet):
         self.norm_kind = check_norm_layer(norm_layer, use_dropout)
         p = check_drop_rate(0.5 if drop_rate is None else drop_rate)
         self._drop_state = None  # device int64 {seed, offset}: a plain attribute, the state_dict keys stay the reference's
+        self.no_conv_t = nct = check_flag("no_conv_t", no_conv_t)
         unet_block = UnetSkipConnectionBlock(ngf * 8, ngf * 8, input_nc=None, submodule=None,
-                                             norm_layer=norm_layer, innermost=True)
+                                             norm_layer=norm_layer, innermost=True, no_conv_t=nct)
         for _ in range(num_downs - 5):
             unet_block = UnetSkipConnectionBlock(ngf * 8, ngf * 8, input_nc=None, submodule=unet_block,
-                                                 norm_layer=norm_layer, use_dropout=bool(use_dropout), drop_rate=p)
+                                                 norm_layer=norm_layer, use_dropout=bool(use_dropout), drop_rate=p,
+                                                 no_conv_t=nct)
         unet_block = UnetSkipConnectionBlock(ngf * 4, ngf * 8, input_nc=None, submodule=unet_block,
-                                             norm_layer=norm_layer)
+                                             norm_layer=norm_layer, no_conv_t=nct)
         unet_block = UnetSkipConnectionBlock(ngf * 2, ngf * 4, input_nc=None, submodule=unet_block,
-                                             norm_layer=norm_layer)
+                                             norm_layer=norm_layer, no_conv_t=nct)
         unet_block = UnetSkipConnectionBlock(ngf, ngf * 2, input_nc=None, submodule=unet_block,
-                                             norm_layer=norm_layer)
+                                             norm_layer=norm_layer, no_conv_t=nct)
         self.model = UnetSkipConnectionBlock(out_channels, ngf, input_nc=in_channels, submodule=unet_block,
-                                             outermost=True, norm_layer=norm_layer)
+                                             outermost=True, norm_layer=norm_layer, no_conv_t=nct)
+
+    def conv_t_state_dict(self):
+        """The state_dict of the equivalent plain ST-CGAN generator (ConvTranspose2d up layers): each up layer's
+        ``N.1.weight`` [cout, cin, 3, 3] becomes ``N.weight`` [cin, cout, 4, 4] (upconv_to_conv_t), ``N.1.bias``
+        becomes ``N.bias``, everything else is copied.  Loads into the reference's STCGAN/networks.py generator and
+        into this module's default one, which then computes what this generator computes.  A generator that already
+        has ConvTranspose2d up layers returns a copy of its state_dict."""
+        sd = self.state_dict()
+        up = {}  # key prefix of each Upsample + Conv2d up layer -> its Conv2d
+        for name, m in self.named_modules():
+            if isinstance(m, nn.Sequential) and len(m) == 2 and isinstance(m[0], nn.Upsample):
+                up[name + ".1."] = name + "."
+        out = type(sd)()
+        for key, v in sd.items():
+            pre = next((p for p in up if key.startswith(p)), None)
+            if pre is None:
+                out[key] = v.detach().clone()
+            elif key == pre + "weight":
+                out[up[pre] + "weight"] = upconv_to_conv_t(v)
+            else:
+                out[up[pre] + key[len(pre):]] = v.detach().clone()
+        return out
 
     def _make_plan(self):
         return engine.GenPlan(self)
@@ -265,7 +322,7 @@ class UnetSkipConnectionBlock(nn.Module):
     Executed only as part of UnetGenerator (the whole U-Net is one fused HIP schedule)."""
 
     def __init__(self, outer_nc, inner_nc, input_nc=None, submodule=None, outermost=False, innermost=False,
-                 norm_layer=nn.BatchNorm2d, use_dropout=False, drop_rate=0.5):
+                 norm_layer=nn.BatchNorm2d, use_dropout=False, drop_rate=0.5, no_conv_t=False):
         super().__init__()
         self.outermost = outermost
         self.innermost = innermost
@@ -277,14 +334,21 @@ class UnetSkipConnectionBlock(nn.Module):
         downnorm = norm_layer(inner_nc)
         uprelu = nn.ReLU(True)
         upnorm = norm_layer(outer_nc)
+
+        def up(cin, cout, bias=True):
+            if no_conv_t:  # resize-convolution (src/models/opt_layers.py:39-56, with zero padding)
+                return nn.Sequential(nn.Upsample(scale_factor=2, mode="nearest"),
+                                     nn.Conv2d(cin, cout, kernel_size=3, stride=1, padding=1, bias=bias))
+            return nn.ConvTranspose2d(cin, cout, kernel_size=4, stride=2, padding=1, bias=bias)
+
         if outermost:
-            upconv = nn.ConvTranspose2d(inner_nc * 2, outer_nc, kernel_size=4, stride=2, padding=1)
+            upconv = up(inner_nc * 2, outer_nc)
             model = [downconv, submodule, uprelu, upconv, nn.Tanh()]
         elif innermost:
-            upconv = nn.ConvTranspose2d(inner_nc, outer_nc, kernel_size=4, stride=2, padding=1, bias=use_bias)
+            upconv = up(inner_nc, outer_nc, bias=use_bias)
             model = [downrelu, downconv, uprelu, upconv, upnorm]
         else:
-            upconv = nn.ConvTranspose2d(inner_nc * 2, outer_nc, kernel_size=4, stride=2, padding=1, bias=use_bias)
+            upconv = up(inner_nc * 2, outer_nc, bias=use_bias)
             model = [downrelu, downconv, downnorm, submodule, uprelu, upconv, upnorm]
             if use_dropout:  # last, as the reference: indices 0-6 and every state_dict key unchanged
                 model.append(nn.Dropout(check_drop_rate(drop_rate)))

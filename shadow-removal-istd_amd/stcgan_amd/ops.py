@@ -598,7 +598,18 @@ def wgrad(B, stride, Dv, R, Gv, Cg, Cg_out, dt, dpro=None, dslope=None, gpro=Non
     return dW
 
 
-_PHASED = {L.PACK_CONV_DGRAD, L.PACK_CONVT_FWD}
+_PHASED = {L.PACK_CONV_DGRAD, L.PACK_CONVT_FWD, L.PACK_UPCONV_FWD}
+# the ConvT operands of a resize-convolution up layer, made from its conv weight [Co][Ci][3][3]
+_UPCONV = {L.PACK_UPCONV_FWD, L.PACK_UPCONV_DGRAD}
+
+
+def _pack_pq(mode, W):
+    """(P, Q) of stc_pack_weight for weight W: its two leading extents; (Ci, Co) of a [Co][Ci][3][3] conv weight
+    for the UPCONV modes (the extents of the ConvT weight it stands for)."""
+    if mode in _UPCONV:
+        assert tuple(W.shape[2:]) == (3, 3), "UPCONV pack modes take a [Co][Ci][3][3] weight"
+        return W.shape[1], W.shape[0]
+    return W.shape[0], W.shape[1]
 
 
 # bumped whenever a packed-operand buffer is created or dropped: the optimiser's cached pointer tables
@@ -612,9 +623,10 @@ def invalidate_packs():
 
 
 def pack(mode, W, n_pad, c_pad, dt):
-    """Pack a torch weight [P][Q][4][4] into the GEMM operand layout [phases][n_pad][taps][c_pad]."""
+    """Pack a torch weight [P][Q][4][4] (UPCONV modes: [Co][Ci][3][3]) into the GEMM operand layout
+    [phases][n_pad][taps][c_pad]."""
     invalidate_packs()
-    P, Q = W.shape[0], W.shape[1]
+    P, Q = _pack_pq(mode, W)
     nph, taps = (4, 4) if mode in _PHASED else (1, 16)
     out = torch.empty((nph, n_pad, taps, c_pad), dtype=dt, device=W.device)
     Wc = W.detach()
@@ -688,7 +700,7 @@ def refresh_packs(cache):
             out = hit[1]
         Wc = W.detach()
         assert Wc.is_contiguous()
-        jobs.setdefault(dt, []).append((L.PackDesc(mode, W.shape[0], W.shape[1], n_pad, c_pad, 0, Wc.data_ptr(),
+        jobs.setdefault(dt, []).append((L.PackDesc(mode, *_pack_pq(mode, W), n_pad, c_pad, 0, Wc.data_ptr(),
                                                    out.data_ptr()), key, ver, out))
     for dt, lst in jobs.items():
         for i in range(0, len(lst), L.PACK_MAX):
@@ -697,6 +709,26 @@ def refresh_packs(cache):
             check(lib().stc_pack_weights(L.dtype_code(dt), len(chunk), arr, stream()), "stc_pack_weights")
             for _, key, ver, out in chunk:
                 cache[key] = (ver, out)
+
+
+def upconv_expand(w3):
+    """The ConvTranspose2d(4, 2, 1) weight [Ci][Co][4][4] equivalent to the resize-convolution weight w3
+    [Co][Ci][3][3] (nearest 2x upsampling + zero-padded 3x3 conv): stc_upconv_expand, fp32, fixed summation order."""
+    assert w3.dim() == 4 and tuple(w3.shape[2:]) == (3, 3) and w3.dtype == torch.float32
+    w3 = w3.detach().contiguous()
+    Co, Ci = w3.shape[0], w3.shape[1]
+    W4 = torch.empty((Ci, Co, 4, 4), dtype=torch.float32, device=w3.device)
+    check(lib().stc_upconv_expand(ptr(w3), Ci, Co, ptr(W4), stream()), "stc_upconv_expand")
+    return W4
+
+
+def upconv_wgrad_collapse(dW4, out):
+    """out [Co][Ci][3][3] (contiguous fp32, any 4-byte aligned slice) = the adjoint of upconv_expand applied to
+    the ConvT-layout gradient dW4 [Ci][Co][4][4]."""
+    Ci, Co = dW4.shape[0], dW4.shape[1]
+    assert tuple(out.shape) == (Co, Ci, 3, 3) and out.is_contiguous() and dW4.is_contiguous()
+    check(lib().stc_upconv_wgrad_collapse(ptr(dW4), Ci, Co, ptr(out), stream()), "stc_upconv_wgrad_collapse")
+    return out
 
 
 def stats_chunks(B, H, W):

@@ -152,6 +152,11 @@ def check_freeze_norm(v):
     return bool(v)
 
 
+def check_nn_upconv(v):
+    """args.NN_upconv as a bool (True / False / 0 / 1; ValueError otherwise)."""
+    return networks.check_flag("args.NN_upconv", v)
+
+
 class STCGAN(object):
 
     def __init__(self, args, train_loader=None, valid_loader=None):
@@ -184,8 +189,12 @@ class STCGAN(object):
         amsgrad = getattr(args, "amsgrad", False)
         if not isinstance(amsgrad, (bool, int)) or amsgrad not in (0, 1):
             raise ValueError(f"stcgan_amd: args.amsgrad must be a bool, got {amsgrad!r}")
-        self.G1 = networks.get_generator(in_channels=3, out_channels=1, ngf=ngf, **nl, **drop)
-        self.G2 = networks.get_generator(in_channels=3 + 1, out_channels=3, ngf=ngf, **nl, **drop)
+        # args.NN_upconv (False; the --NN-upconv option of the reference's src/ line): both generators' up layers are
+        # nearest-neighbour upsampling + 3x3 conv instead of ConvTranspose2d (networks.UnetGenerator, no_conv_t)
+        self.NN_upconv = check_nn_upconv(getattr(args, "NN_upconv", False))
+        up = dict(no_conv_t=True) if self.NN_upconv else {}
+        self.G1 = networks.get_generator(in_channels=3, out_channels=1, ngf=ngf, **nl, **drop, **up)
+        self.G2 = networks.get_generator(in_channels=3 + 1, out_channels=3, ngf=ngf, **nl, **drop, **up)
         self.D1 = networks.get_discriminator(in_channels=3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False, **nl)
         self.D2 = networks.get_discriminator(in_channels=3 + 3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False, **nl)
         tasks = getattr(args, "tasks", ["train"])

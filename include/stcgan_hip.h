@@ -26,6 +26,8 @@
  *                    STCGAN/networks.py UnetSkipConnectionBlock: counter-based Philox masks, nothing stored
  *   stc_bn_bwd_frozen / stc_bn_running_rstd  BatchNorm2d backward on running statistics (module in eval mode, or frozen
  *                    under a train-mode network), one pass: the same reference lines with training=False
+ *   stc_bn_stats_pack / stc_bn_bwd_sums / stc_bn_bwd_apply_sync  nn.SyncBatchNorm (norm_layer=nn.SyncBatchNorm): the
+ *                    same reference lines with the statistics taken over all data-parallel ranks
  *   stc_tanh_bias_bwd Tanh backward + outermost ConvT bias grad (networks.py:112-116)
  *   stc_gather_nchw / stc_scatter_nchw              torch.cat input concat (stcgan.py:219-227,269-272) / its backward
  *   stc_loss_fwd / stc_loss_bwd                     DataLoss (L1) and AdversarialLoss (MSE / BCE-with-logits), loss.py:14-26,59-86
@@ -415,6 +417,28 @@ int stc_bn_bwd_frozen(int dtype, int B, stc_view x, int C,
                       stc_view g1, float slope1, stc_view g2, float slope2, const stc_dropout* drop /* NULL: none */,
                       float* part, int nchunks,
                       stc_view dx, float* dgamma, float* dbeta, void* stream);
+
+/* ---- sync statistics: nn.SyncBatchNorm, batch statistics over all data-parallel ranks (one process per GPU) ----
+ * The caller moves the records between the ranks (one all-gather per normed layer and direction); every rank then
+ * reads the same records in rank order, so every rank ends with the same bits.
+ * stc_bn_stats_pack: one rank's nchunks chunk partials [chunk][C]{n, S1, S2, shift} (stc_chan_stats, or a conv's
+ *   fused statistics) merged -- the merge of stc_bn_finalize: fp64, fixed order, the same lane policies -- into one
+ *   record per channel rec[C]{n, S1, S2, shift} with shift = fl32(mean): it loses the fp32 rounding of S1 and S2 and
+ *   nothing else.  stc_bn_finalize(records of all ranks [world][C][4], nchunks = world, ...) then gives mean / rstd /
+ *   table and the running update of the global batch (the count comes from the records: ranks may differ in batch).
+ * stc_bn_bwd_sums: part2 of stc_bn_bwd_reduce[_drop] / stc_conv_bwd_bn -> this rank's dbeta / dgamma (both NULL: not
+ *   wanted), the bits stc_bn_bwd_apply writes from that part2, and rec[C]{sum dn, sum dn*xhat}, the same values.
+ * stc_bn_bwd_apply_sync: recs [world][C][2] are added in rank order (fp64, rounded to fp32) to the global S1 = sum dn
+ *   and S2 = sum dn*xhat; dx = gamma*rstd*(dn - S1/count - xhat*S2/count), count the global pixel count, dn as in
+ *   stc_bn_bwd_apply (drop != NULL: as in stc_bn_bwd_apply_drop, g1 required).  With world = 1 and count = B*H*W it
+ *   is bit-identical to stc_bn_bwd_apply / stc_bn_bwd_apply_drop on the same inputs.                            */
+int stc_bn_stats_pack(const float* part, int nchunks, int C, float* rec, void* stream);
+int stc_bn_bwd_sums(const float* part2, int nchunks, int C, float* dgamma, float* dbeta, float* rec, void* stream);
+int stc_bn_bwd_apply_sync(int dtype, int B, stc_view x, int C,
+                          const float* scale, const float* shift, const float* mean, const float* rstd,
+                          const float* gamma,
+                          stc_view g1, float slope1, stc_view g2, float slope2, const stc_dropout* drop /* NULL: none */,
+                          const float* recs, int world, int64_t count, stc_view dx, void* stream);
 
 /* y = tanh(q) stored NCHW fp32 (the generator output).  dq = gy*(1-y^2) into NHWC
  * view dq; dbias[c] = sum dq (deterministic).                               */

@@ -9,6 +9,9 @@
 // Backward: dn = g1*act1'(n) + g2*act2'(n) is recomputed on the fly from the raw
 // input (n = x*scale + shift), reduced to sum(dn), sum(dn*xhat), then applied.
 // On running statistics (eval mode / frozen layers) dx = scale*dn needs no sum: one pass (stc_bn_bwd_frozen).
+// Sync statistics (nn.SyncBatchNorm): stc_bn_stats_pack turns a rank's partials into one record
+// per channel, stc_bn_finalize over the ranks' records is the global finalize; backward, stc_bn_bwd_sums emits the
+// rank's sums as a record and stc_bn_bwd_apply_sync applies the sum of the ranks' records with the global count.
 // All reductions are fixed-order => bitwise reproducible.
 //
 // Each piece is stated once and the kernels are thin users of it, but for the reduction layout, which
@@ -19,8 +22,11 @@
 //   bn_bwd_reduce_body   the backward's chunk reduction, with or without the dx store (bn_bwd_reduce, and
 //                        bn_bwd_frozen_sums: running statistics, where that one pass is the whole backward)
 //   bn_fwd_emit          the forward per element: n, the optional mask, one or two activations
-//   bn_bwd_table/_dx     the backward per element: the k0/k1/k2 table and dx from (v, g1, g2, mask); dn_term is
-//                        one gradient's term of dn (dn_add: of a whole vector, as the reduce adds it)
+//   bn_bwd_table/_dx     the backward per element: the k0/k1/k2 table (bn_bwd_coef: from loaded values) and dx from
+//                        (v, g1, g2, mask); dn_term is one gradient's term of dn (dn_add: of a whole vector, as the
+//                        reduce adds it)
+//   bn_merge_stats / bn_bwd_merge  the two chunk merges as bodies, for the sync kernels (bn_finalize_kernel and
+//                        bn_bwd_finalize_kernel keep their own, pinned, copies)
 #include <type_traits>
 
 #include "common.hpp"
@@ -226,6 +232,86 @@ template <class R> static dim3 merge_grid(int C) { return dim3((C + R::CPB - 1) 
 // chunk mean m_b = shift + S1/n, chunk M2_b = S2 - S1^2/n; then (exactly, in fp64)
 //   mean = sum n_b m_b / N,   M2 = sum [M2_b + n_b (m_b - mean)^2]
 // in two passes over the chunks (the policy's lanes per channel, fixed-order tree -> deterministic).
+// The merge itself, for the kernels added after bn_finalize_kernel (which keeps its own copy below: through this body
+// the compiler schedules it differently, and its code is pinned): pre_load(c), the caller's own loads for channel c,
+// issued with the partials' loads; emit(c, N, mean, M2) on lane 0.
+template <class R, class Pre, class Emit>
+__device__ __forceinline__ void bn_merge_stats(const float* part, int nchunks, int C, Pre&& pre_load, Emit&& emit) {
+  constexpr int L = R::LANES;
+  const int lane = R::lane(), c = R::channel();
+  if (R::CPB > 1 && c >= C) return;
+  // chunk partials are read in groups of 4 per lane (the 4 loads in flight together: one
+  // memory latency per group -- the first layers merge up to 4096 chunks per channel)
+  auto load4 = [&](int k0, float4* pp) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = k0 + u * L;
+      pp[u] = k < nchunks ? *reinterpret_cast<const float4*>(part + ((long long)k * C + c) * 4)
+                          : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  pre_load(c);
+  auto sum1 = [&](const float4* pp, double& n, double& sm) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (pp[u].x <= 0.f) continue;
+      n += pp[u].x;
+      sm += (double)pp[u].x * pp[u].w + (double)pp[u].y;  // n_b * m_b = n_b*shift + S1
+    }
+  };
+  auto sum2 = [&](const float4* pp, double mu, double& m2) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (pp[u].x <= 0.f) continue;
+      const double nb = pp[u].x, s1 = pp[u].y, r = s1 / nb;
+      double q = (double)pp[u].z - s1 * r;
+      if (q < 0) q = 0;
+      const double d = (double)pp[u].w + r - mu;
+      m2 += q + nb * d * d;
+    }
+  };
+  // up to 16 L chunks: every lane loads its (up to) 4 groups of 4 partials at once and keeps them in registers
+  // for both passes (one memory latency); the sums run in the loop's order below, so the results are the same
+  auto in_regs = [&](auto Gc, double& n, double& sm, double& m2) {
+    constexpr int G = decltype(Gc)::value;
+    float4 pp[G][4];
+#pragma unroll
+    for (int g = 0; g < G; ++g) load4(lane + 4 * L * g, pp[g]);
+#pragma unroll
+    for (int g = 0; g < G; ++g) sum1(pp[g], n, sm);
+    n = R::sum(n);
+    sm = R::sum(sm);
+    const double mu = n > 0 ? sm / n : 0.0;
+#pragma unroll
+    for (int g = 0; g < G; ++g) sum2(pp[g], mu, m2);
+    return mu;
+  };
+  double n = 0, sm = 0, m2 = 0, mu;
+  if (nchunks <= 4 * L) {
+    mu = in_regs(std::integral_constant<int, 1>{}, n, sm, m2);
+  } else if (nchunks <= 8 * L) {
+    mu = in_regs(std::integral_constant<int, 2>{}, n, sm, m2);
+  } else if (nchunks <= 16 * L) {
+    mu = in_regs(std::integral_constant<int, 4>{}, n, sm, m2);
+  } else {
+    for (int k0 = lane; k0 < nchunks; k0 += 4 * L) {
+      float4 pp[4];
+      load4(k0, pp);
+      sum1(pp, n, sm);
+    }
+    n = R::sum(n);
+    sm = R::sum(sm);
+    mu = n > 0 ? sm / n : 0.0;
+    for (int k0 = lane; k0 < nchunks; k0 += 4 * L) {
+      float4 pp[4];
+      load4(k0, pp);
+      sum2(pp, mu, m2);
+    }
+  }
+  const double M2 = R::sum(m2);
+  if (lane == 0) emit(c, n, mu, M2);
+}
+
 template <class R>
 __global__ void __launch_bounds__(256) bn_finalize_kernel(const float* part, int nchunks, int C,
                                                           const float* gamma, const float* beta,
@@ -307,6 +393,22 @@ __global__ void __launch_bounds__(256) bn_finalize_kernel(const float* part, int
   if (lane == 0) bn_finalize_store(c, n, mu, M2, pre, rmean, rvar, nbt, momentum, eps, mean_o, rstd_o, scale, shift);
 }
 
+// Sync statistics: one rank's chunk partials merged into ONE record per channel, in the partials' own format, so that
+// stc_bn_finalize over the ranks' records (nchunks = world) gives the statistics of the global batch.  From the merged
+// (N, mean, M2), all fp64: shift = fl32(mean), d = mean - shift (|d| <= ulp(mean)/2),
+//   rec = {N, S1 = N d, S2 = M2 + N d^2, shift}
+// which the merge reads back as mean_b = shift + S1/N = mean and M2_b = S2 - S1^2/N = M2: exactly, but for the fp32
+// rounding of S1 (a relative 2^-24 of at most half an ulp of the mean) and of S2 (a relative 2^-24 of M2).  N is
+// exact below 2^24 pixels per rank.
+template <class R>
+__global__ void __launch_bounds__(256) bn_stats_pack_kernel(const float* part, int nchunks, int C, float* rec) {
+  bn_merge_stats<R>(part, nchunks, C, [](int) {}, [&](int c, double n, double mu, double M2) {
+    const float sh = (float)mu;
+    const double d = mu - (double)sh;
+    *reinterpret_cast<float4*>(rec + (long long)c * 4) = make_float4((float)n, (float)(n * d), (float)(M2 + n * d * d), sh);
+  });
+}
+
 // eval-mode table from running statistics
 __global__ void bn_eval_table_kernel(int C, const float* gamma, const float* beta, const float* rmean,
                                      const float* rvar, float eps, float* scale, float* shift) {
@@ -343,6 +445,16 @@ __device__ __forceinline__ void dn_add(const float* g, const float* m, const flo
 // MASKED: g1 is required and carries the dropout factor m.
 // CHECKED = false: the entry point has required every table (the _drop calls), so the tests for an absent scale or
 // mean are compiled out -- behind them the compiler contracts k0's products differently and dx's last bit moves.
+template <int N>
+__device__ __forceinline__ void bn_bwd_coef(const float* mu, const float* rs, const float* gm, const float* dg,
+                                            const float* db, float invP, float* k0, float* k1, float* k2) {
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    k1[e] = gm[e] * rs[e];
+    k2[e] = k1[e] * rs[e] * dg[e] * invP;
+    k0[e] = k1[e] * (db[e] * invP - mu[e] * rs[e] * dg[e] * invP);
+  }
+}
 template <int N, bool CHECKED = true>
 __device__ __forceinline__ void bn_bwd_table(int c, const float* scale, const float* shift, const float* mean,
                                              const float* rstd, const float* gamma, const float* dgamma,
@@ -353,12 +465,7 @@ __device__ __forceinline__ void bn_bwd_table(int c, const float* scale, const fl
   if (!CHECKED || mean) {
     float mu[N], rs[N], gm[N], dg[N], db[N];
     ldc<N>(mean + c, mu); ldc<N>(rstd + c, rs); ldc<N>(gamma + c, gm); ldc<N>(dgamma + c, dg); ldc<N>(dbeta + c, db);
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-      k1[e] = gm[e] * rs[e];
-      k2[e] = k1[e] * rs[e] * dg[e] * invP;
-      k0[e] = k1[e] * (db[e] * invP - mu[e] * rs[e] * dg[e] * invP);
-    }
+    bn_bwd_coef<N>(mu, rs, gm, dg, db, invP, k0, k1, k2);
   } else {
 #pragma unroll
     for (int e = 0; e < N; ++e) { k1[e] = 1.f; k2[e] = 0.f; k0[e] = 0.f; }
@@ -457,6 +564,32 @@ __global__ void __launch_bounds__(256) bn_bwd_frozen_sums_kernel(View x, PixDiv 
 }
 
 // dbeta[c] = sum dn, dgamma[c] = sum dn*xhat  (fixed order over chunks, the policy's lanes per channel)
+// (the merge of bn_bwd_finalize_kernel, which keeps its own copy for the same reason as bn_finalize_kernel:)
+// emit(c, sum dn, sum dn*xhat) on lane 0
+template <class R, class Emit>
+__device__ __forceinline__ void bn_bwd_merge(const float* part, int nchunks, int C, Emit&& emit) {
+  constexpr int L = R::LANES;
+  const int lane = R::lane(), c = R::channel();
+  if (R::CPB > 1 && c >= C) return;
+  double a = 0, b = 0;
+  for (int k0 = lane; k0 < nchunks; k0 += 4 * L) {  // groups of 4 loads in flight
+    float2 pp[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = k0 + u * L;
+      pp[u] = k < nchunks ? *reinterpret_cast<const float2*>(part + ((long long)k * C + c) * 2) : make_float2(0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      a += pp[u].x;
+      b += pp[u].y;
+    }
+  }
+  a = R::sum(a);
+  b = R::sum(b);
+  if (lane == 0) emit(c, a, b);
+}
+
 template <class R>
 __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(const float* part, int nchunks, int C, float* dgamma,
                                                               float* dbeta) {
@@ -483,6 +616,20 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(const float* part,
     dbeta[c] = (float)a;
     dgamma[c] = (float)b;
   }
+}
+
+// Sync statistics: the same merge; this rank's dbeta / dgamma (absent: no parameter gradient wanted) and the record
+// rec[c] = {sum dn, sum dn*xhat}, the same fp32 values, for the exchange
+template <class R>
+__global__ void __launch_bounds__(256) bn_bwd_sums_kernel(const float* part, int nchunks, int C, float* dgamma,
+                                                          float* dbeta, float* rec) {
+  bn_bwd_merge<R>(part, nchunks, C, [&](int c, double a, double b) {
+    if (dgamma) {
+      dbeta[c] = (float)a;
+      dgamma[c] = (float)b;
+    }
+    *reinterpret_cast<float2*>(rec + (long long)c * 2) = make_float2((float)a, (float)b);
+  });
 }
 
 template <typename T, bool DENSE>
@@ -840,6 +987,51 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_drop_kernel(View x, PixDiv p
     bn_bwd_table<N, false>(c, scale, shift, mean, rstd, gamma, dgamma, dbeta, invP, sc, sh, k0, k1, k2);
     mask.template factor<N>(key, mask.index(C, b, yy, xx, c), m);
     bn_bwd_dx<N, true>(gi, sc, sh, k0, k1, k2, v, g1, g2, m, d);
+    Vec16<T>::store(reinterpret_cast<T*>(dx.p) + vidx(dx, b, yy, xx, c), d);
+  }
+}
+
+// Sync statistics (the batch spread over `world` data-parallel ranks): bn_bwd_apply_kernel / bn_bwd_apply_drop_kernel
+// with the sums of the GLOBAL batch -- each thread adds the ranks' records {sum dn, sum dn*xhat} of its channels in
+// rank order (fp64, then fp32: with one record, that record) -- and 1 / count, the global pixel count, for 1 / P.
+// General addressing, as the _drop kernel: the layers that run it carry one small collective each anyway.
+template <typename T, class M>
+__global__ void __launch_bounds__(256) bn_bwd_apply_sync_kernel(View x, PixDiv pd, long long P, int C,
+                                                                const float* scale, const float* shift,
+                                                                const float* mean, const float* rstd,
+                                                                const float* gamma, GradIn gi, const float* recs,
+                                                                int world, long long count, View dx, M mask) {
+  constexpr int N = Vec16<T>::N;
+  const int CG = C / N;
+  const long long total = P * CG;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const float invP = 1.f / (float)count;
+  const typename M::Key key = mask.key();
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
+    const int c = N * (int)(idx % CG);
+    int b, yy, xx;
+    pix_bxy(pd, idx / CG, b, yy, xx);
+    float v[N], g1[N], g2[N], m[N], d[N];
+    Vec16<T>::load(vptr<T>(x, b, yy, xx, c), v);
+    if (M::ON || gi.has1) Vec16<T>::load(vptr<T>(gi.g1, b, yy, xx, c), g1);
+    if (gi.has2) Vec16<T>::load(vptr<T>(gi.g2, b, yy, xx, c), g2);
+    float sc[N], sh[N], mu[N], rs[N], gm[N], dg[N], db[N], k0[N], k1[N], k2[N];
+    ldc<N>(scale + c, sc); ldc<N>(shift + c, sh);
+    ldc<N>(mean + c, mu); ldc<N>(rstd + c, rs); ldc<N>(gamma + c, gm);
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      double a = 0, q = 0;
+      for (int r = 0; r < world; ++r) {  // rank order: every rank forms the same sums
+        const float2 s = *reinterpret_cast<const float2*>(recs + ((long long)r * C + c + e) * 2);
+        a += s.x;
+        q += s.y;
+      }
+      db[e] = (float)a;
+      dg[e] = (float)q;
+    }
+    bn_bwd_coef<N>(mu, rs, gm, dg, db, invP, k0, k1, k2);
+    if constexpr (M::ON) mask.template factor<N>(key, mask.index(C, b, yy, xx, c), m);
+    bn_bwd_dx<N, M::ON>(gi, sc, sh, k0, k1, k2, v, g1, g2, m, d);
     Vec16<T>::store(reinterpret_cast<T*>(dx.p) + vidx(dx, b, yy, xx, c), d);
   }
 }
@@ -1264,6 +1456,56 @@ extern "C" int stc_bn_bwd_frozen(int dtype, int B, stc_view x, int C, const floa
   else if (drop) STC_FZ(false, PhiloxMask, mask);
   else STC_FZ(false, NoMask, NoMask{});
 #undef STC_FZ
+  STC_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- sync statistics (nn.SyncBatchNorm: batch statistics over all data-parallel ranks)
+extern "C" int stc_bn_stats_pack(const float* part, int nchunks, int C, float* rec, void* stream) {
+  STC_REQUIRE(part && rec && nchunks > 0 && C > 0, "stc_bn_stats_pack: partials of nchunks > 0 chunks, C > 0 and a record buffer required");
+  hipStream_t st = (hipStream_t)stream;
+  // (the lane policies of stc_bn_finalize)
+  if (nchunks <= 1024) hipLaunchKernelGGL(bn_stats_pack_kernel<WaveMerge>, merge_grid<WaveMerge>(C), dim3(256), 0, st, part, nchunks, C, rec);
+  else hipLaunchKernelGGL(bn_stats_pack_kernel<BlockMerge>, merge_grid<BlockMerge>(C), dim3(256), 0, st, part, nchunks, C, rec);
+  STC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stc_bn_bwd_sums(const float* part2, int nchunks, int C, float* dgamma, float* dbeta, float* rec,
+                               void* stream) {
+  STC_REQUIRE(part2 && rec && nchunks > 0 && C > 0, "stc_bn_bwd_sums: partials of nchunks > 0 chunks, C > 0 and a record buffer required");
+  STC_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), "stc_bn_bwd_sums: dgamma / dbeta must come together");
+  hipStream_t st = (hipStream_t)stream;
+  // (the lane policies of bwd_finalize)
+  if (nchunks <= 256) hipLaunchKernelGGL(bn_bwd_sums_kernel<WaveMerge>, merge_grid<WaveMerge>(C), dim3(256), 0, st, part2, nchunks, C, dgamma, dbeta, rec);
+  else hipLaunchKernelGGL(bn_bwd_sums_kernel<BlockMerge>, merge_grid<BlockMerge>(C), dim3(256), 0, st, part2, nchunks, C, dgamma, dbeta, rec);
+  STC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stc_bn_bwd_apply_sync(int dtype, int B, stc_view x, int C, const float* scale, const float* shift,
+                                     const float* mean, const float* rstd, const float* gamma, stc_view g1,
+                                     float slope1, stc_view g2, float slope2, const stc_dropout* drop,
+                                     const float* recs, int world, int64_t count, stc_view dx, void* stream) {
+  STC_REQUIRE(vec_ok(dtype, C, x) && dx.p && vec_ok(dtype, C, dx) && (!g1.p || vec_ok(dtype, C, g1)) &&
+                  (!g2.p || vec_ok(dtype, C, g2)),
+              "stc_bn_bwd_apply_sync: bad C=%d / views", C);
+  STC_REQUIRE(mean && rstd && gamma && scale && shift && recs, "stc_bn_bwd_apply_sync: missing BN tensors / records");
+  const Pixels s = pixels_of(dtype, B, x, C);
+  STC_REQUIRE(world >= 1 && count >= s.P, "stc_bn_bwd_apply_sync: world=%d, count=%lld: at least one rank and at least this rank's %lld pixels",
+              world, (long long)count, s.P);
+  PhiloxMask mask;
+  if (drop) {
+    STC_REQUIRE(g1.p, "stc_bn_bwd_apply_sync: a dropout block needs g1, the gradient that passes through it");
+    if (int rc = mkdrop(drop, B, C, &mask.d, "stc_bn_bwd_apply_sync")) return rc;
+    STC_REQUIRE(x.H <= drop->H && x.W <= drop->W, "stc_bn_bwd_apply_sync: view outside the dropout extent");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  GradIn gi = mkgrad(g1, slope1, g2, slope2);
+  View o = mkview(dx);
+  const int blocks = grid_for(s.work);
+  if (drop) STC_DT(dtype, hipLaunchKernelGGL((bn_bwd_apply_sync_kernel<T_, PhiloxMask>), dim3(blocks), dim3(256), 0, st, s.v, s.pd, s.P, C, scale, shift, mean, rstd, gamma, gi, recs, world, (long long)count, o, mask));
+  else STC_DT(dtype, hipLaunchKernelGGL((bn_bwd_apply_sync_kernel<T_, NoMask>), dim3(blocks), dim3(256), 0, st, s.v, s.pd, s.P, C, scale, shift, mean, rstd, gamma, gi, recs, world, (long long)count, o, NoMask{}));
   STC_CHECK_LAUNCH();
   return 0;
 }

@@ -125,6 +125,10 @@ _SIGS = {
     "stc_bn_running_rstd": (_i32, [_i32, _vp, _f32, _vp, _vp]),
     "stc_bn_bwd_frozen": (_i32, [_i32, _i32, View, _i32, _vp, _vp, _vp, _vp, View, _f32, View, _f32, _vp, _vp, _i32,
                                  View, _vp, _vp, _vp]),
+    "stc_bn_stats_pack": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "stc_bn_bwd_sums": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "stc_bn_bwd_apply_sync": (_i32, [_i32, _i32, View, _i32, _vp, _vp, _vp, _vp, _vp, View, _f32, View, _f32, _vp,
+                                     _vp, _i32, _i64, View, _vp]),
     "stc_tanh_bias_bwd": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, View, _vp, _vp, _i32, _vp]),
     "stc_gather_nchw": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, View, _i32, _vp]),
     "stc_scatter_nchw": (_i32, [_i32, _i32, _i32, _i32, View, _i32, _vp, _vp, _vp]),

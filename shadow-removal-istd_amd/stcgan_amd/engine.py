@@ -33,8 +33,12 @@ DESIGN.md section 8e): conv, the eval table (+ rstd_run when a backward follows)
 the input-gradient conv, then one frozen-statistics backward (one pass; the sums only where parameter gradients are
 wanted).
 
+nn.SyncBatchNorm layers with more than one data-parallel rank: the BatchNorm forms split where
+the statistics are merged, with one small all-gather of per-channel records there -- per normed layer one in the
+forward and one in the backward, issued in the same host order on every rank.
+
 Every place where a conv meets a norm layer goes through two functions, whatever the norm and its mode (_IN, _BATCH,
-_RUNNING): _conv_norm_act forward and _conv_act_norm_backward backward, which name the library calls of each form.
+_RUNNING, _SYNC): _conv_norm_act forward and _conv_act_norm_backward backward, which name the library calls of each form.
 The latter is also the one place where a conv's weight is released to the optimiser (GradWriter.done) after its last
 read.
 """
@@ -44,6 +48,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from . import parallel
 from .ops import LRELU
 
 # ----------------------------------------------------------------------------- tracing (tests)
@@ -275,6 +280,7 @@ class GenPlan:
         self.co = [c.out_channels for c in conv]
         # which norm the network uses: BatchNorm2d, or InstanceNorm2d (affine or not)
         self.inorm, self.affine = _norm_kind(list(bnd.values()) + list(bnu.values()))
+        self.sync, self.norm_names = _sync_kind(list(bnd.values()) + list(bnu.values()), names)
         self.params = list(net.parameters())
 
 
@@ -325,6 +331,18 @@ def _norm_kind(norms):
     return inorm, inorm and any(m.weight is not None for m in norms)
 
 
+def _sync_kind(norms, names):
+    """(nn.SyncBatchNorm layers?, {id(norm): its module name}) of a network's norm modules; a SyncBatchNorm bound
+    to a process group of its own is refused (the records travel over the default group)."""
+    sync = [m for m in norms if isinstance(m, torch.nn.SyncBatchNorm)]
+    assert not sync or len(sync) == len(norms)
+    for m in sync:
+        if m.process_group is not None:
+            raise NotImplementedError(f"stcgan_amd: nn.SyncBatchNorm layer {names.get(id(m), '?')} has a process_group "
+                                      "of its own: only the default process group is supported")
+    return bool(sync), {id(m): names.get(id(m), "?") for m in norms}
+
+
 def _check_plane(B, C, h, w):
     """torch's refusal of an instance norm over one spatial element (train and eval alike), before any launch."""
     if h * w <= 1:
@@ -334,22 +352,57 @@ def _check_plane(B, C, h, w):
 
 # ----------------------------------------------------------------------------- the normed-layer step
 # How the norm layers of one network call normalise: instance norm (one mode); BatchNorm on batch statistics;
-# BatchNorm on its running statistics (eval mode, or frozen under a train-mode network).
-_IN, _BATCH, _RUNNING = 0, 1, 2
+# BatchNorm on its running statistics (eval mode, or frozen under a train-mode network); nn.SyncBatchNorm layers on
+# the batch statistics of all data-parallel ranks (only with a process group of more than one rank: else _BATCH, the
+# very same launches as nn.BatchNorm2d's).
+_IN, _BATCH, _RUNNING, _SYNC = 0, 1, 2, 3
 
 
 def _norm_mode(plan, batch_stats):
-    return _IN if plan.inorm else (_BATCH if batch_stats else _RUNNING)
+    if plan.inorm:
+        return _IN
+    if not batch_stats:
+        return _RUNNING
+    return _SYNC if (plan.sync and parallel.world() > 1) else _BATCH
 
 
-def _conv_norm_act(kind, B, xv, cin, w, cout, yv, dt, norm, mode, apply_x, y1, s1, y2, s2, drop, defer, keep):
+class _Sync:
+    """What the _SYNC layers of one network call share: the global batch size (the ranks' local batches may differ)
+    and the call's list of collectives, [(norm layer, "forward" / "backward")] in host order, appended to
+    ``net.sync_log`` when that is a list -- every rank must issue the same sequence (tests compare the lists)."""
+
+    def __init__(self, plan, B, dev):
+        self.Bg = parallel.global_batch(B, dev)
+        self.names = plan.norm_names
+        self.calls = []
+        log = getattr(plan.net, "sync_log", None)
+        if log is not None:
+            log.append(self.calls)
+
+    def count(self, xv):
+        """Pixels per channel of the global batch over xv's extent (the same on every rank)."""
+        return self.Bg * xv.H * xv.W
+
+    def gather(self, norm, direction):
+        def run(rec):
+            self.calls.append((self.names[id(norm)], direction))
+            return parallel.gather_records(rec)
+        return run
+
+
+def _conv_norm_act(kind, B, xv, cin, w, cout, yv, dt, norm, mode, apply_x, y1, s1, y2, s2, drop, defer, keep,
+                   sync=None):
     """Conv into ``yv`` -> norm layer ``norm`` -> activation pass of ``apply_x`` (yv or its top-left crop) into y1 [and
     y2] (y1 None: no pass).  Returns ((2, cout) scale / shift table or None, (mean, rstd) or None).
     _BATCH: one library call, the statistics out of the conv itself; ``defer`` (a list): the running statistics are not
     updated, the update's inputs are appended (bn_running_update).  _RUNNING: conv, the table from the running
     statistics, the apply pass; ``keep`` (a backward will follow): (running_mean, rstd_run) beside the table.  _IN:
     conv, then the statistics of the stored raw output with the pass; no table.  ``drop``: a dropout level between a
-    BatchNorm and the activation (dropout_next)."""
+    BatchNorm and the activation (dropout_next).  _SYNC (``sync``: the call's _Sync): the split form of _BATCH with
+    one gather of the ranks' records between the partials and the table; ``defer`` gets the gathered records."""
+    if mode == _SYNC:
+        return ops.conv_bn_act_sync(kind, B, xv, cin, w, cout, yv, dt, norm, apply_x, y1, s1, y2, s2, defer, drop,
+                                    sync.gather(norm, "forward"))
     if mode == _BATCH:
         return ops.conv_bn_act(kind, B, xv, cin, w, cout, yv, dt, norm, apply_x, y1, s1, y2, s2, defer, drop)
     ops.conv(kind, B, xv, cin, w, cout, yv, dt)
@@ -364,7 +417,7 @@ def _conv_norm_act(kind, B, xv, cin, w, cout, yv, dt, norm, mode, apply_x, y1, s
 
 
 def _conv_act_norm_backward(kind, B, gv, cg, wd, cin, gt, yv, dt, norm, mode, tab, st, xv, C, s_self, g_other, s_other,
-                            ch_off, dxv, drop, own, W, lane):
+                            ch_off, dxv, drop, own, W, lane, sync=None):
     """The backward of one layer boundary: the input-gradient conv (kind, gv with cg channels, packed weight wd, cin
     output channels) into the view ``yv`` of tensor ``gt``, then the backward of the activation(s) and of the norm
     layer ``norm`` (None: none) that produced the conv's input, into ``dxv``.  xv: the norm's input (C channels),
@@ -379,7 +432,8 @@ def _conv_act_norm_backward(kind, B, gv, cg, wd, cin, gt, yv, dt, norm, mode, ta
     _IN                    conv, in_backward
     _RUNNING               conv, bn_backward_frozen (through ``drop`` where there is one)
     _BATCH with ``drop``   conv, bn_backward (the GEMM epilogues know nothing of the mask)
-    _BATCH                 the BatchNorm reduction fused into the conv (conv_bn_backward)"""
+    _BATCH                 the BatchNorm reduction fused into the conv (conv_bn_backward)
+    _SYNC                  as _BATCH, in the split forms with one gather of the ranks' sums before the apply"""
     if norm is None:
         # (no epilogue form under TRACE, which wants the conv's own output, or where the conv writes a larger extent
         # than the activation's: an odd generator level)
@@ -390,7 +444,7 @@ def _conv_act_norm_backward(kind, B, gv, cg, wd, cin, gt, yv, dt, norm, mode, ta
             return
         fused = False
     else:
-        fused = mode == _BATCH and drop is None
+        fused = mode in (_BATCH, _SYNC) and drop is None
     if not fused:
         ops.conv(kind, B, gv, cg, wd, cin, yv, dt)
         if W is not None and norm is not None:
@@ -408,7 +462,13 @@ def _conv_act_norm_backward(kind, B, gv, cg, wd, cin, gt, yv, dt, norm, mode, ta
     dgamma = dbeta = None
     if W is not None and norm.weight is not None:
         dgamma, dbeta = W.dest(norm.weight), W.dest(norm.bias)
-    if fused:
+    if fused and mode == _SYNC:
+        ops.conv_bn_backward_sync(kind, B, gv, cg, wd, cin, yv, dt, xv, C, (tab[0], tab[1], st[0], st[1]), norm.weight,
+                                  s_self, ch_off, g_other, s_other, dxv, dgamma, dbeta, sync.count(xv),
+                                  sync.gather(norm, "backward"))
+        if W is not None:
+            W.done(own, lane)
+    elif fused:
         ops.conv_bn_backward(kind, B, gv, cg, wd, cin, yv, dt, xv, C, (tab[0], tab[1], st[0], st[1]), norm.weight,
                              s_self, ch_off, g_other, s_other, dxv, dgamma, dbeta)
         if W is not None:
@@ -418,6 +478,9 @@ def _conv_act_norm_backward(kind, B, gv, cg, wd, cin, gt, yv, dt, norm, mode, ta
     elif mode == _RUNNING:
         ops.bn_backward_frozen(B, xv, C, dt, dxv, g1, s1, g2, s2, (tab[0], tab[1], st[0], st[1]), dgamma, dbeta,
                                W is not None, drop)
+    elif mode == _SYNC:
+        ops.bn_backward_sync(B, xv, C, dt, dxv, g1, s1, g2, s2, (tab[0], tab[1], st[0], st[1], norm.weight), dgamma,
+                             dbeta, drop, sync.count(xv), sync.gather(norm, "backward"))
     else:
         ops.bn_backward(B, xv, C, dt, dxv, g1, s1, g2, s2, (tab[0], tab[1], st[0], st[1], norm.weight), dgamma, dbeta,
                         drop)
@@ -471,6 +534,7 @@ def gen_forward(plan, sources, train, dt, cache, save, batch_stats=None):
     rq = [None] + [_nhwc(B, *_pad2(S, k), co[k - 1], dt, dev) for k in range(1, Lv)]
     tab_d, tab_u, st_d, st_u = {}, {}, {}, {}
     mode = _norm_mode(plan, batch_stats)
+    sync = _Sync(plan, B, dev) if mode == _SYNC else None
 
     # use_dropout, train mode: this call's {seed, offset} copy (one tiny launch; the generator's offset advances),
     # read from device memory by every dropout kernel of the call, forward and backward
@@ -499,7 +563,7 @@ def gen_forward(plan, sources, train, dt, cache, save, batch_stats=None):
         if k <= Lv - 2:
             av = L.nhwc_view(ad[k])
             t, st_d[k] = _conv_norm_act(L.CONV_S2, B, xv, co[k - 1], wk, co[k], rv, dt, plan.bnd[k], mode, rv, av,
-                                        LRELU, L.nhwc_view(cr[k], 0), 0.0, None, None, save)
+                                        LRELU, L.nhwc_view(cr[k], 0), 0.0, None, None, save, sync)
             if t is not None:
                 tab_d[k] = t
         else:  # innermost: no down-norm (STCGAN/networks.py:118-124)
@@ -511,7 +575,7 @@ def gen_forward(plan, sources, train, dt, cache, save, batch_stats=None):
         # statistics over the full ConvT extent (before the crop of an odd level)
         t, st_u[k] = _conv_norm_act(L.CONVT_S2, B, L.nhwc_view(cr[k]), cin_t(k), wt, co[k - 1], L.nhwc_view(rq[k]), dt,
                                     plan.bnu[k], mode, L.nhwc_view(rq[k], 0, *S[k]),
-                                    L.nhwc_view(cr[k - 1], co[k - 1]), 0.0, None, 0.0, drop_of(k), None, save)
+                                    L.nhwc_view(cr[k - 1], co[k - 1]), 0.0, None, 0.0, drop_of(k), None, save, sync)
         if t is not None:
             tab_u[k] = t
     # ---- outermost: tanh(convT_0(cr[0]) + bias) -> NCHW fp32
@@ -524,7 +588,7 @@ def gen_forward(plan, sources, train, dt, cache, save, batch_stats=None):
     if save:
         saved = dict(S=S, xin=xin, rd=rd, ad=ad, cr=cr, rq=rq, tab_d=tab_d, tab_u=tab_u, st_d=st_d, st_u=st_u,
                      y=y, cin=cin, cin_pad=cin_pad, src_c=[s.shape[1] for s in sources],
-                     frozen=not (plan.inorm or batch_stats))
+                     frozen=not (plan.inorm or batch_stats), sync=sync)
         if drop_state is not None:
             saved["drop"] = {k: drop_of(k) for k in plan.drop}
         if TRACE is not None:
@@ -545,7 +609,8 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
     need_w = W is not None
     lane = _WgradLane() if need_w else None
     drops = saved.get("drop") or {}  # {level: dropout level of the forward call} (use_dropout, train mode)
-    mode = _norm_mode(plan, not saved["frozen"])
+    mode, sync = _norm_mode(plan, not saved["frozen"]), saved["sync"]
+    assert (mode == _SYNC) == (sync is not None), "the process group changed between a forward and its backward"
     # ---- tanh + bias
     cp = ops.vec(dt)
     Ho, Wo = y.shape[2], y.shape[3]
@@ -590,7 +655,7 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
         dq = _nhwc(B, ah, aw, C, dt, dev)
         _conv_act_norm_backward(L.CONV_S2, B, dqv, cg, wd, cin_t, gcat[k], L.nhwc_view(gcat[k], 0, *S[k + 1]), dt,
                                 plan.bnu[k + 1], mode, tab_u.get(k + 1), st_u[k + 1], L.nhwc_view(rq[k + 1]), C, 0.0,
-                                None, 0.0, C, L.nhwc_view(dq), drops.get(k + 1), [wT], W, lane)
+                                None, 0.0, C, L.nhwc_view(dq), drops.get(k + 1), [wT], W, lane, sync)
         _trace("G", ("dq", k + 1), dq)
     # ---- innermost r_{L-1}: ReLU backward (no BN)
     dr = _nhwc(B, *S[Lv], co[Lv - 1], dt, dev)
@@ -625,7 +690,7 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
         dr = _nhwc(B, *S[k], cprev, dt, dev)
         _conv_act_norm_backward(L.CONVT_S2, B, drv, co[k], wd, cprev, ga, L.nhwc_view(ga), dt, plan.bnd.get(j), mode,
                                 tab_d.get(j), st_d.get(j), L.nhwc_view(rd[j]), cprev, LRELU,
-                                L.nhwc_view(gcat[j], 0, *S[k]), 0.0, 0, L.nhwc_view(dr), None, [wk], W, lane)
+                                L.nhwc_view(gcat[j], 0, *S[k]), 0.0, 0, L.nhwc_view(dr), None, [wk], W, lane, sync)
     if lane is not None:
         lane.join()
     return src_grads
@@ -641,10 +706,12 @@ class DiscPlan:
         self.net = net
         seq = net.model
         convs = [m for m in seq if isinstance(m, torch.nn.Conv2d)]
-        bns = [m for m in seq if isinstance(m, (torch.nn.BatchNorm2d, torch.nn.InstanceNorm2d))]
+        bns = [m for m in seq if isinstance(m, (torch.nn.BatchNorm2d, torch.nn.SyncBatchNorm,
+                                                torch.nn.InstanceNorm2d))]
         assert len(convs) == len(bns) + 2
         self.convs, self.bns = convs, bns
         self.inorm, self.affine = _norm_kind(bns)
+        self.sync, self.norm_names = _sync_kind(bns, {id(m): n for n, m in net.named_modules()})
         self.n = len(convs)
         self.strides = [c.stride[0] for c in convs]
         self.in_c = convs[0].in_channels
@@ -696,6 +763,7 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
     raw, act, dims, chans, tabs, stats = [xin], [xin], [(H, W)], [cin_pad], [None], [None]
     out = None
     mode = _norm_mode(plan, batch_stats)
+    sync = _Sync(plan, B, dev) if mode == _SYNC else None
     xv = L.nhwc_view(xin)  # (of act[i], the input of conv_i)
     for i, cv in enumerate(plan.convs):
         s = plan.strides[i]
@@ -721,7 +789,7 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
             ov = L.nhwc_view(o)
             # (stats_only: only the logits layer reads the last activation -- no pass)
             t, st = _conv_norm_act(kind, B, xv, chans[i], wp, cout, ov, dt, plan.bns[i - 1], mode, ov,
-                                   None if (stats_only and i == n - 2) else av, LRELU, None, 0.0, None, defer, save)
+                                   None if (stats_only and i == n - 2) else av, LRELU, None, 0.0, None, defer, save, sync)
             if t is not None:
                 tab = (t[0], t[1])
         elif ops.conv_act(kind, B, xv, chans[i], wp, cout, av, LRELU, dt, bias=cv.bias):
@@ -741,7 +809,7 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
     saved = None
     if save:
         saved = dict(raw=raw, act=act, dims=dims, chans=chans, tabs=tabs, stats=stats, cin=cin, cin_pad=cin_pad,
-                     bias_ch=bias_ch, frozen=not (plan.inorm or batch_stats),
+                     bias_ch=bias_ch, frozen=not (plan.inorm or batch_stats), sync=sync,
                      src_c=[s.shape[1] for s in sources])
         if TRACE is not None:
             _trace_new("D")
@@ -765,7 +833,8 @@ def disc_backward(plan, saved, gout, dt, cache, need_src, W):
     gch = cp
     src_grads = None
     lane = _WgradLane() if need_w else None
-    mode = _norm_mode(plan, not saved["frozen"])
+    mode, sync = _norm_mode(plan, not saved["frozen"]), saved["sync"]
+    assert (mode == _SYNC) == (sync is not None), "the process group changed between a forward and its backward"
     for i in range(n - 1, -1, -1):
         cv = plan.convs[i]
         s = plan.strides[i]
@@ -813,7 +882,7 @@ def disc_backward(plan, saved, gout, dt, cache, need_src, W):
         _trace("D", ("ga", i), ga)
         _conv_act_norm_backward(dkind, B, gv, gch, wd, cin, ga, L.nhwc_view(ga), dt,
                                 plan.bns[i - 2] if i >= 2 else None, mode, tabs[i], stats[i], L.nhwc_view(raw[i]), cin,
-                                LRELU, None, 0.0, 0, L.nhwc_view(gn), None, own, W, lane)
+                                LRELU, None, 0.0, 0, L.nhwc_view(gn), None, own, W, lane, sync)
         g, gch, h, w = gn, cin, ph, pw
     if lane is not None:
         lane.join()

@@ -7,7 +7,10 @@ layers inside the tree only hold parameters and buffers; ``forward`` of the
 network runs the whole network as hand-written HIP kernels
 (``engine.gen_forward`` / ``engine.disc_forward``) behind one autograd node.
 
-``norm_layer``: nn.BatchNorm2d (default), nn.InstanceNorm2d, or a functools.partial of nn.InstanceNorm2d with
+``norm_layer``: nn.BatchNorm2d (default), nn.SyncBatchNorm (the BatchNorm2d tree and keys; with torch.distributed
+initialised and more than one rank its train-mode statistics run over the batches of all ranks, one small collective per
+normed layer and direction, default process group only; otherwise exactly BatchNorm2d -- also a BatchNorm2d network
+converted by ``nn.SyncBatchNorm.convert_sync_batchnorm`` before its first forward), nn.InstanceNorm2d, or a functools.partial of nn.InstanceNorm2d with
 ``affine`` and/or ``eps`` (instance statistics in train and eval mode; no buffers); anything else raises.
 
 Differences from the reference that a caller can observe: none in values
@@ -36,6 +39,8 @@ import torch.nn as nn
 from . import engine
 from . import ops
 
+# the norm modules with batch / running statistics (nn.SyncBatchNorm is no subclass of nn.BatchNorm2d)
+_BATCH_NORMS = (nn.BatchNorm2d, nn.SyncBatchNorm)
 _DTYPES = {"fp32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}
 
 
@@ -69,18 +74,28 @@ def check_drop_rate(p):
 
 
 def check_norm_layer(norm_layer, use_dropout=False):
-    """'batch' for nn.BatchNorm2d, 'instance' for nn.InstanceNorm2d or a functools.partial of it (affine and/or eps);
+    """'batch' for nn.BatchNorm2d, 'sync_batch' for nn.SyncBatchNorm (default process group), 'instance' for nn.InstanceNorm2d or a functools.partial of it (affine and/or eps);
     NotImplementedError for anything else.  Decided from the constructed module, as the layers will be."""
     if norm_layer is nn.BatchNorm2d:
         return "batch"
+    if norm_layer is nn.SyncBatchNorm:
+        return "sync_batch"
     name = getattr(getattr(norm_layer, "func", norm_layer), "__name__", repr(norm_layer))
     try:
         m = norm_layer(8)
     except Exception:
         m = None
+    if type(m) is nn.SyncBatchNorm:  # (a functools.partial of it)
+        if m.process_group is not None:
+            raise NotImplementedError("stcgan_amd: nn.SyncBatchNorm with a process_group of its own is not supported "
+                                      "(the statistics travel over the default process group)")
+        if not (m.affine and m.track_running_stats):
+            raise NotImplementedError("stcgan_amd: nn.SyncBatchNorm with affine=False or track_running_stats=False "
+                                      "is not supported")
+        return "sync_batch"
     if type(m) is not nn.InstanceNorm2d:
         raise NotImplementedError(f"stcgan_amd: norm_layer {name if m is None else type(m).__name__} is not on the "
-                                  "ST-CGAN path (nn.BatchNorm2d, nn.InstanceNorm2d or a functools.partial of "
+                                  "ST-CGAN path (nn.BatchNorm2d, nn.SyncBatchNorm, nn.InstanceNorm2d or a functools.partial of "
                                   "nn.InstanceNorm2d with affine / eps)")
     if m.track_running_stats:
         raise NotImplementedError("stcgan_amd: nn.InstanceNorm2d with track_running_stats=True is not supported "
@@ -140,6 +155,9 @@ class _HipNet(nn.Module):
         # alone and append what ops.bn_running_update needs to apply the update later (the trainer orders it after
         # another call's, as the reference's call order has it)
         self.defer_running = None
+        # a list (tests, diagnostics): every call on sync statistics appends its list of collectives,
+        # [(norm layer name, "forward" / "backward")] in host order (engine._Sync)
+        self.sync_log = None
 
     def set_compute_dtype(self, dtype):
         """'fp32' (default, parity path) or 'bf16' (bf16 operands, fp32 accumulation/BN/master weights)."""
@@ -169,7 +187,7 @@ class _HipNet(nn.Module):
         ``training`` flags, all alike.  Instance norm has one mode: the network's flag, which nothing reads."""
         named = self._bn_named
         if named is None:  # (the module tree is fixed at construction)
-            named = self._bn_named = [(n, m) for n, m in self.named_modules() if isinstance(m, nn.BatchNorm2d)]
+            named = self._bn_named = [(n, m) for n, m in self.named_modules() if isinstance(m, _BATCH_NORMS)]
         on = sum(m.training for _, m in named)
         if on == len(named):
             return bool(named) or self.training
@@ -186,7 +204,7 @@ class _HipNet(nn.Module):
         the network's mode.  ``net.train()`` / ``net.eval()`` reset every child, as in torch: call this after
         them.  No effect on the computation of instance-norm networks.  Returns self."""
         for m in self.modules():
-            if isinstance(m, (nn.BatchNorm2d, nn.InstanceNorm2d)):
+            if isinstance(m, _BATCH_NORMS + (nn.InstanceNorm2d,)):
                 m.training = self.training and not on
         return self
 

@@ -815,6 +815,110 @@ def bn_backward(B, xv, C, dt, dxv, g1=None, s1=0.0, g2=None, s2=0.0, bn_state=No
     return dgamma, dbeta
 
 
+# ----------------------------------------------------------------------------- sync statistics (nn.SyncBatchNorm)
+# The split forms of conv_bn_act / conv_bn_backward / bn_backward with one exchange between "partials" and "table / dx"
+# (DESIGN.md section 8g): every rank packs its partials into one record per channel, the records of all ranks are
+# gathered in rank order (parallel.gather_records, one collective on the current stream) and every rank finishes
+# from the same records -- the same bits everywhere.
+
+
+def bn_stats_pack(part, nch, C):
+    """One record {n, S1, S2, shift} per channel from this rank's ``nch`` chunk partials (stc_bn_stats_pack)."""
+    rec = torch.empty((C, 4), dtype=torch.float32, device=part.device)
+    check(lib().stc_bn_stats_pack(ptr(part), nch, C, ptr(rec), stream()), "stc_bn_stats_pack")
+    return rec
+
+
+def bn_bwd_sums(part2, nch, C, dgamma=None, dbeta=None):
+    """This rank's dbeta / dgamma (into ``dgamma`` / ``dbeta`` when given, else not written) and the record
+    [C, 2] = {sum dn, sum dn * xhat} of the backward reduce's partials (stc_bn_bwd_sums)."""
+    rec = torch.empty((C, 2), dtype=torch.float32, device=part2.device)
+    check(lib().stc_bn_bwd_sums(ptr(part2), nch, C, ptr(dgamma), ptr(dbeta), ptr(rec), stream()), "stc_bn_bwd_sums")
+    return rec
+
+
+def bn_bwd_apply_sync(B, xv, C, dt, dxv, g1, s1, g2, s2, bn_state, recs, count, drop=None):
+    """dx of a BatchNorm on the statistics of ``count`` pixels spread over the ranks whose records
+    ``recs`` [world, C, 2] holds (stc_bn_bwd_apply_sync); bn_state = (scale, shift, mean, rstd, gamma)."""
+    scale, shift, mean, rstd, gamma = bn_state
+    d = _drop(drop) if drop is not None else None
+    assert recs.dim() == 3 and tuple(recs.shape[1:]) == (C, 2) and recs.is_contiguous()
+    check(lib().stc_bn_bwd_apply_sync(L.dtype_code(dt), B, xv, C, ptr(scale), ptr(shift), ptr(mean), ptr(rstd),
+                                      ptr(gamma), g1 if g1 is not None else L.NULL_VIEW, float(s1),
+                                      g2 if g2 is not None else L.NULL_VIEW, float(s2),
+                                      ctypes.byref(d) if d is not None else None, ptr(recs), recs.shape[0], int(count),
+                                      dxv, stream()), "stc_bn_bwd_apply_sync")
+
+
+def conv_bn_act_sync(kind, B, xv, cin, w_packed, cout, yv, dt, bn, apply_x, y1, s1, y2=None, s2=0.0, defer=None,
+                     drop=None, gather=None):
+    """conv_bn_act on the statistics of all ranks: conv with its partials, pack, gather, the finalize over the ranks'
+    records (every rank updates its running statistics with the global, unbiased-by-the-global-count values) and the
+    activation pass.  defer (a list): (gathered records, world, cout, bn) is appended for bn_running_update."""
+    upd = defer is None
+    t = torch.empty((2, cout), dtype=torch.float32, device=w_packed.device)
+    part, nch = conv_stats(kind, B, xv, cin, w_packed, cout, yv, dt)
+    recs = gather(bn_stats_pack(part, nch, cout))
+    st = bn_finalize_part(recs, recs.shape[0], cout, bn, t[0], t[1], update_running=upd)
+    if not upd:
+        defer.append((recs, recs.shape[0], cout, bn))
+    if y1 is not None:
+        bn_apply(B, apply_x, cout, dt, (t[0], t[1]), y1, s1, y2, s2, drop=drop)
+    return t, st
+
+
+def conv_bn_backward_sync(kind, B, xv, cin, w_packed, cout, yv, dt, bn_x, C, bn_state, gamma, s_self, ch_off, g_other,
+                          s_other, dxv, dgamma, dbeta, count, gather):
+    """conv_bn_backward on the statistics of all ranks: the input-gradient conv with the BatchNorm reduction fused in
+    (stc_conv_bwd_bn), this rank's sums, the gather, the apply on the global sums."""
+    dev = w_packed.device
+    l = lib()
+    gh, gw = (xv.H, xv.W) if kind == L.CONVT_S2 else (yv.H, yv.W)
+    ws, nb = _ws(_conv_ws_bytes(kind, B, gh, gw, cin, cout, dt), dev)
+    scale, shift, mean, rstd = bn_state
+    fuse = L.BnbFuse(bn_x, g_other if g_other is not None else L.NULL_VIEW, scale.data_ptr(), shift.data_ptr(),
+                     mean.data_ptr(), rstd.data_ptr(), float(s_self), float(s_other), C, ch_off)
+    key = ("bnbch", kind, B, cin, cout, dt, L.layout_key(xv), L.layout_key(yv), bn_x.H, bn_x.W, g_other is None)
+    nch = _MEMO.get(key)
+    if nch is None:
+        nch = _MEMO[key] = l.stc_conv_bwd_bn_chunks_ex(L.dtype_code(dt), kind, B, xv, cin, cout, yv,
+                                                       ctypes.byref(fuse))
+        check(0 if nch > 0 else -1, "stc_conv_bwd_bn_chunks_ex")
+    part = torch.empty((nch, C, 2), dtype=torch.float32, device=dev)
+    check(l.stc_conv_bwd_bn(L.dtype_code(dt), kind, B, xv, cin, ptr(w_packed), cout, yv, ctypes.byref(fuse),
+                            ptr(part), nch, ptr(ws), nb, stream()), "stc_conv_bwd_bn")
+    recs = gather(bn_bwd_sums(part, nch, C, dgamma, dbeta))
+    # g1 = the conv output at the BN channels over the BN extent (as conv_bn_backward's split form)
+    g1 = L.View(yv.p, bn_x.H, bn_x.W, yv.bs, yv.rs, yv.ps, yv.co + ch_off, yv.cs, 0)
+    g1._keep = yv
+    # the kernels form g1 * act1' + g2 * act2' in this order: another consumer's gradient first
+    a1 = (g1, s_self, None, 0.0)
+    if g_other is not None:
+        a1 = (g_other, s_other, g1, s_self)
+    bn_bwd_apply_sync(B, bn_x, C, dt, dxv, *a1, (scale, shift, mean, rstd, gamma), recs, count)
+
+
+def bn_backward_sync(B, xv, C, dt, dxv, g1, s1, g2, s2, bn_state, dgamma, dbeta, drop, count, gather):
+    """bn_backward on the statistics of all ranks: the reduce (through ``drop`` where there is one), this rank's sums,
+    the gather, the apply on the global sums."""
+    l = lib()
+    scale, shift, mean, rstd, gamma = bn_state
+    g1v = g1 if g1 is not None else L.NULL_VIEW
+    g2v = g2 if g2 is not None else L.NULL_VIEW
+    nch = stats_chunks(B, xv.H, xv.W)
+    part = torch.empty((nch, C, 2), dtype=torch.float32, device=scale.device)
+    if drop is not None:
+        d = _drop(drop)
+        check(l.stc_bn_bwd_reduce_drop(L.dtype_code(dt), B, xv, C, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), g1v,
+                                       float(s1), g2v, float(s2), ctypes.byref(d), ptr(part), nch, stream()),
+              "stc_bn_bwd_reduce_drop")
+    else:
+        check(l.stc_bn_bwd_reduce(L.dtype_code(dt), B, xv, C, ptr(scale), ptr(shift), ptr(mean), ptr(rstd), g1v,
+                                  float(s1), g2v, float(s2), ptr(part), nch, stream()), "stc_bn_bwd_reduce")
+    recs = gather(bn_bwd_sums(part, nch, C, dgamma, dbeta))
+    bn_bwd_apply_sync(B, xv, C, dt, dxv, g1, s1, g2, s2, bn_state, recs, count, drop)
+
+
 def bn_running_rstd(C, bn, out=None):
     """rstd_run[c] = 1 / sqrt(running_var[c] + eps) of a BatchNorm2d (stc_bn_running_rstd): the factor inside
     bn_eval_table's scale, which the frozen-statistics backward needs on its own for dgamma."""

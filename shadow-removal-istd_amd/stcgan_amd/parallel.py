@@ -106,6 +106,47 @@ def average_scalars(values):
     return {k: t[i] for i, k in enumerate(keys)}
 
 
+def gather_records(rec):
+    """``rec`` of every rank, stacked in rank order: ``[world, *rec.shape]``, the same bits on every rank (sync
+    BatchNorm statistics).  One collective on the current stream: it starts after what that stream
+    has queued (the kernel that wrote ``rec``), and what the stream queues next waits for it -- on the main stream and
+    on the discriminator lanes alike.  RCCL: all_gather_into_tensor.  gloo cannot all-gather device tensors: every
+    rank writes its slot of a zero-filled buffer and the buffers are summed, which is exact (every other addend of
+    an element is +0; a -0 arrives as +0).  World 1: no collective."""
+    w = world()
+    if w == 1:
+        return rec.unsqueeze(0)
+    rec = rec.contiguous()
+    if dist.get_backend() == "nccl":
+        out = torch.empty((w,) + tuple(rec.shape), dtype=rec.dtype, device=rec.device)
+        dist.all_gather_into_tensor(out, rec)
+        return out
+    out = torch.zeros((w,) + tuple(rec.shape), dtype=rec.dtype, device=rec.device)
+    out[rank()].copy_(rec)
+    dist.all_reduce(out, op=dist.ReduceOp.SUM)
+    return out
+
+
+# {local batch size: global batch size} for the network calls of one train step (set and cleared by the trainer: its
+# calls of one step all see the same batches), or None
+STEP_BATCH = None
+
+
+def global_batch(B, device):
+    """The number of samples all ranks together feed to this network call (sync BatchNorm: the count of the backward;
+    local batches may differ).  One tiny collective and a host read, unless the trainer has answered for the step."""
+    if world() == 1:
+        return int(B)
+    if STEP_BATCH is not None and B in STEP_BATCH:
+        return STEP_BATCH[B]
+    t = torch.tensor([int(B)], dtype=torch.int64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    n = int(t.item())
+    if STEP_BATCH is not None:
+        STEP_BATCH[B] = n
+    return n
+
+
 class FlatGrads:
     """The parameter gradients of one network in one flat fp32 buffer; ``view(p)`` is the slice that
     becomes ``p.grad``.  Parameters are laid out in reverse module order, which is the order their

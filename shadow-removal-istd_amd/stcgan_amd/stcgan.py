@@ -152,6 +152,17 @@ def check_freeze_norm(v):
     return bool(v)
 
 
+_NORM_LAYERS = {"batch": torch.nn.BatchNorm2d, "instance": torch.nn.InstanceNorm2d,
+                "sync_batch": torch.nn.SyncBatchNorm}
+
+
+def check_norm(v):
+    """The norm_layer of args.norm: "batch", "instance" or "sync_batch" (ValueError otherwise)."""
+    if not isinstance(v, str) or v not in _NORM_LAYERS:
+        raise ValueError(f"stcgan_amd: args.norm must be 'batch', 'instance' or 'sync_batch', got {v!r}")
+    return _NORM_LAYERS[v]
+
+
 def check_nn_upconv(v):
     """args.NN_upconv as a bool (True / False / 0 / 1; ValueError otherwise)."""
     return networks.check_flag("args.NN_upconv", v)
@@ -169,11 +180,12 @@ class STCGAN(object):
         # only; infer() ignores it), its masks drawn from each generator's device-resident {seed, offset}
         self.use_dropout = bool(getattr(args, "use_dropout", False))
         drop = dict(use_dropout=True, drop_rate=getattr(args, "droprate", 0.5)) if self.use_dropout else {}
-        # args.norm: "batch" (default) or "instance" -- the norm_layer of all four networks
+        # args.norm: "batch" (default), "instance" or "sync_batch" -- the norm_layer of all four networks.
+        # "sync_batch" (nn.SyncBatchNorm): with more than one rank the train-mode statistics of every BatchNorm layer run
+        # over the batches of all ranks (one small collective per normed layer and direction; no graph capture then);
+        # with one rank it is "batch"
         self.norm = getattr(args, "norm", "batch")
-        if self.norm not in ("batch", "instance"):
-            raise ValueError(f"stcgan_amd: args.norm must be 'batch' or 'instance', got {self.norm!r}")
-        nl = dict(norm_layer=torch.nn.InstanceNorm2d if self.norm == "instance" else torch.nn.BatchNorm2d)
+        nl = dict(norm_layer=check_norm(self.norm))
         # args.freeze_norm (False): train steps run with the BatchNorm layers of all four networks on their running
         # statistics, which then never move (fine-tuning a checkpoint on few images or at batch size 1-2); dropout,
         # where configured, stays active.  No effect with args.norm = "instance".
@@ -474,10 +486,13 @@ class STCGAN(object):
             self.D1.grad_consumer = self.D2.grad_consumer = main
         # each discriminator sees the same real and fake inputs in the D and the G step: gather them once
         self.D1.input_cache, self.D2.input_cache = {}, {}
+        if self.norm == "sync_batch":  # every network call of the step sees these batches: one global count
+            parallel.STEP_BATCH = {}
         try:
             return self._step(x, m, y, training, acc, main, l1, l2, weight)
         finally:
             self.D1.input_cache = self.D2.input_cache = None
+            parallel.STEP_BATCH = None
 
     def _step(self, x, m, y, training, acc, main, l1, l2, weight=1.0):
         with torch.set_grad_enabled(training):
@@ -623,6 +638,9 @@ class STCGAN(object):
         step (tests/test_gpu_graph.py).  World size > 1 needs the RCCL backend (collectives are captured
         too)."""
         import torch.distributed as dist
+        if parallel.world() > 1 and self.norm == "sync_batch":
+            raise NotImplementedError("STCGAN.capture: args.norm = 'sync_batch' with more than one rank is not "
+                                      "supported (its per-layer collectives are not captured into a graph)")
         if parallel.world() > 1 and dist.get_backend() != "nccl":
             raise RuntimeError("STCGAN.capture: multi-process capture needs the nccl (RCCL) backend")
         main, l1, l2 = self._lanes()

@@ -112,7 +112,10 @@ int stc_conv_fwd_plan(int dtype, int kind, int B, int Hg, int Wg, int Cin, int C
  * stats_part (optional): [stats_chunks][Cout][4] partials in stc_chan_stats format, merged by
  * stc_bn_finalize.  bf16 operands run on the LDS-DMA MFMA kernel, which computes the partials
  * in its epilogue (or in the split-K reduction); other cases run stc_conv_fwd + stc_chan_stats.
- * force_plan (optional, tuning/tests): {tile config, ksplit} for the bf16 kernel.
+ * force_plan (optional, tuning/tests): NULL or {-1, .} automatic; {100, shape} the halo kernel (an error where it
+ * is not eligible); {-2, .} the automatic im2col tile; {tile config >= 0, ksplit} that tile; for the narrow
+ * (Cout <= 8) kernels {tile rows, 16-column blocks}.  Which kernel runs, in what order the conditions are
+ * tried, and the workspace and chunk count that follow: the conv dispatch table of DESIGN.md section 4.
  * stc_conv_fwd_query returns the workspace bytes, the number of partial-stat chunks and the
  * plan {BM, BN, ksplit, narrow_n, tile config} for the same arguments.                       */
 int stc_conv_fwd_query(int dtype, int kind, int B, int Hg, int Wg, int Cin, int Cout, int out_f32,
@@ -134,7 +137,8 @@ int stc_conv_fwd_ex(int dtype, int kind, int B, stc_view x, int Cin, const void*
  * the GEMM epilogue / split-K reduction; other cases run the conv and stc_bn_bwd_reduce.
  * stc_conv_bwd_bn_chunks_ex: the part2 chunk count for the same arguments (the kernel that runs, and so
  * the count, depends on the views' layout); stc_conv_bwd_bn_chunks: the same from the shape alone, for dense
- * 16-byte NHWC views at channel offset 0 (and no second gradient on the 31 x 31 logits-layer gradient).   */
+ * 16-byte NHWC views at channel offset 0 (and no second gradient on the 31 x 31 logits-layer gradient).
+ * Both read the route of the launch itself (the conv dispatch table of DESIGN.md section 4).               */
 typedef struct {
   stc_view x;        /* BN input (raw pre-BN values), C channels, extent = the BN domain  */
   stc_view g_other;  /* optional second gradient into the BN output (p == NULL: none)     */

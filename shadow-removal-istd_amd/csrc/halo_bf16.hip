@@ -30,6 +30,7 @@
 // Epilogue: igemm_bf16.hpp (bias, BatchNorm statistics, the fused BatchNorm-backward sums, 16-byte NHWC stores).
 #include <type_traits>
 
+#include "conv_route.hpp"
 #include "igemm_bf16.hpp"
 
 namespace stc {

@@ -20,6 +20,7 @@
 // Register-staged double buffer: the global loads of K-step s+1 are in flight
 // while step s runs on MFMA; one barrier per step.
 #include "common.hpp"
+#include "conv_route.hpp"
 
 namespace stc {
 
@@ -570,12 +571,14 @@ __global__ void narrow_tiled_kernel(const ConvParams p, int tiles_x, int tiles_p
   }
 }
 
+// narrow_tiled_kernel: ConvT s2 / conv s1, whole 128-byte channel chunks
+bool narrow_tiled_eligible(int dtype, int kind, int Cin) {
+  return (kind == STC_CONVT_S2 || kind == STC_CONV_S1) && Cin % (dtype == STC_F32 ? 32 : 64) == 0;
+}
+
 template <typename T>
-static bool launch_narrow_tiled(int kind, int B, ConvParams& p, hipStream_t st) {
-  const int CC = 128 / sizeof(T);
-  if (p.cin % CC != 0) return false;
-  const int geom = kind == STC_CONVT_S2 ? 0 : (kind == STC_CONV_S1 ? 1 : -1);
-  if (geom < 0) return false;
+static void launch_narrow_tiled(int kind, int B, ConvParams& p, hipStream_t st) {
+  const int geom = kind == STC_CONVT_S2 ? 0 : 1;
   const int TY = geom == 0 ? 16 : 8, TX = geom == 0 ? 16 : 8;
   const int tiles_x = cdiv(p.GW, TX), tiles_y = cdiv(p.GH, TY);
   const int tpi = tiles_x * tiles_y;
@@ -590,7 +593,6 @@ static bool launch_narrow_tiled(int kind, int B, ConvParams& p, hipStream_t st) 
     else hipLaunchKernelGGL((narrow_tiled_kernel<T, 1, 8>), grid, dim3(64), 0, st, p, tiles_x, tpi);
   }
   main_timer_end(st);
-  return true;
 }
 
 // ------------------------------------------------------------------------- host
@@ -600,13 +602,9 @@ static int ilog2_exact(int v) {
   return (1 << l) == v ? l : -1;
 }
 
-struct Plan {
-  int BM, BN, ksplit, kchunk, mtiles, ntiles;
-};
-
-static Plan plan_for(int dtype, int M, int N, int K, int nphase) {
+FpPlan fp_tile_plan(int dtype, int M, int N, int K, int nphase) {
   const int BK = dtype == STC_F32 ? 32 : 64;
-  Plan pl{};
+  FpPlan pl{};
   if (N <= 32) { pl.BM = 128; pl.BN = 32; }
   else if (N <= 64) { pl.BM = 128; pl.BN = 64; }
   else { pl.BM = 128; pl.BN = 128; }
@@ -628,7 +626,7 @@ static Plan plan_for(int dtype, int M, int N, int K, int nphase) {
 static size_t lds_bytes(int BM, int BN) { return 2 * (size_t)(BM + BN) * LDS_ROW + BM * 8; }
 
 template <typename T>
-static int launch_igemm(const Plan& pl, ConvParams& p, hipStream_t st) {
+static int launch_igemm(const FpPlan& pl, ConvParams& p, hipStream_t st) {
   dim3 grid(pl.mtiles * pl.ntiles, 1, p.nphase * pl.ksplit);
   const size_t lds = lds_bytes(pl.BM, pl.BN);
   const bool pro = p.sc != nullptr || p.pro_act != 0;
@@ -656,98 +654,163 @@ static int launch_igemm(const Plan& pl, ConvParams& p, hipStream_t st) {
   return 0;
 }
 
-}  // namespace stc
-
-using namespace stc;
-
-static bool use_smalln(int dtype, int N, int K) {
+bool use_smalln(int dtype, int N, int K) {
   const int esz = dtype == STC_F32 ? 4 : 2;
   return N <= 8 && (long long)N * K * esz <= 64 * 1024;
 }
 
-namespace stc {
-bool bf16_conv_eligible(int kind, int B, const stc_view& x, int Cin, int Cout);
-int bf16_conv_query(int kind, int B, int Hg, int Wg, int Cin, int Cout, int out_f32, const int32_t* force,
-                    int64_t* ws_bytes, int32_t* stats_chunks, int32_t* plan_out);
-int bf16_conv_fwd(int kind, int B, stc_view x, int Cin, const void* w_packed, int Cout, stc_view y,
-                  const float* bias, int epi_tanh, int out_f32, float* stats, int stats_chunks,
-                  const int32_t* force, void* ws, int64_t ws_bytes, hipStream_t st,
-                  const stc_bnb_fuse* bnb = nullptr, float* part2 = nullptr,
-                  const stc_view* act2 = nullptr, int act_n = 0, float act_s1 = 0.f, float act_s2 = 0.f,
-                  int bnb_act = 0);
-bool bf16_conv_act_ok(int kind, int B, const stc_view& x, int Cin, int Cout, const stc_view& y1, const stc_view* y2);
-bool bf16_narrow_eligible(int kind, int Cin, int Cout);
-int64_t bf16_narrow_workspace(int kind, int B, int GH, int GW, int Cin, int Cout);
-int bf16_narrow_fwd(int kind, int B, stc_view x, int Cin, const void* w_packed, int Cout, stc_view y,
-                    const float* bias, int epi_tanh, int out_f32, void* ws, int64_t ws_bytes, hipStream_t st,
-                    const int32_t* force = nullptr);
 }  // namespace stc
 
-// bf16 operands on the LDS-DMA kernel (igemm_bf16.hip) whenever the shape allows (no prologue,
-// N >= 16, 16-byte channel alignment); the query mirrors that decision for an NHWC input view.
-static bool bf16_path(int dtype, int kind, int Cin, int Cout) {
-  if (dtype != STC_BF16) return false;
-  const Geometry g = geometry(kind);
-  const int taps = g.taps_lg_tw == 2 ? 16 : 4;
-  return Cin % 8 == 0 && Cout >= 16 && Cout % 8 == 0 && Cout <= 2048 && !use_smalln(dtype, Cout, taps * Cin);
+using namespace stc;
+
+// ---- asks.  Every entry point below states its call as a ConvAsk, takes the route from conv_route (conv_route.cpp,
+// DESIGN.md section 4) and reads its answer there or launches the kernel it names.
+static ConvAsk conv_ask(int dtype, int kind, int B, const stc_view& x, int Cin, int Cout, const stc_view& y) {
+  ConvAsk a{};
+  a.dtype = dtype; a.kind = kind; a.B = B; a.x = x; a.y = y; a.Cin = Cin; a.Cout = Cout;
+  return a;
 }
 
+// The views the shape-only queries assume, written down once: dense NHWC of the kind's input and output extents for
+// the GEMM grid Hg x Wg, channel offset 0, 16-byte aligned base, no second gradient -- and batch stride 0: a shape
+// has no allocation, so the limits the kernels put on a view's size in memory (2 GiB of input, 2^31 output elements,
+// both growing with B * bs) count as met.  The _ex forms and the launches answer for the real views.
+static stc_view dense_view(int H, int W, int C) {
+  stc_view v{};
+  v.H = H; v.W = W; v.rs = (int64_t)W * C; v.ps = C; v.cs = 1;
+  return v;
+}
+static ConvAsk shape_ask(int dtype, int kind, int B, int Hg, int Wg, int Cin, int Cout) {
+  const int d = kind == STC_CONV_S1 ? 1 : (kind == STC_CONV_S1_DGRAD ? -1 : 0);  // conv s1: 31 x 31 from 32 x 32
+  const stc_view grid = dense_view(Hg, Wg, kind == STC_CONVT_S2 ? Cin : Cout);
+  const stc_view other = kind == STC_CONVT_S2 ? dense_view(2 * Hg, 2 * Wg, Cout)
+                                              : (d ? dense_view(Hg + d, Wg + d, Cin) : dense_view(2 * Hg, 2 * Wg, Cin));
+  return kind == STC_CONVT_S2 ? conv_ask(dtype, kind, B, grid, Cin, Cout, other)
+                              : conv_ask(dtype, kind, B, other, Cin, Cout, grid);
+}
+
+// (the prologue form runs the register-staged kernel where the plain call runs a bf16 one: enough for both)
 extern "C" int64_t stc_conv_fwd_workspace(int dtype, int kind, int B, int Hg, int Wg, int Cin, int Cout) {
-  const Geometry g = geometry(kind);
-  const int taps = g.taps_lg_tw == 2 ? 16 : 4;
-  const int M = B * Hg * Wg, K = taps * Cin;
-  if (use_smalln(dtype, Cout, K))
-    return dtype == STC_BF16 && bf16_narrow_eligible(kind, Cin, Cout) ? bf16_narrow_workspace(kind, B, Hg, Wg, Cin, Cout) : 0;
-  int64_t ws_new = 0;
-  if (bf16_path(dtype, kind, Cin, Cout))  // the prologue form still runs the register-staged kernel: max of both
-    bf16_conv_query(kind, B, Hg, Wg, Cin, Cout, 0, nullptr, &ws_new, nullptr, nullptr);
-  const Plan pl = plan_for(dtype, M, Cout, K, g.nphase);
-  const int64_t ws_old = pl.ksplit <= 1 ? 0 : (int64_t)g.nphase * pl.ksplit * (int64_t)M * Cout * 4;
-  return std::max(ws_old, ws_new);
+  ConvAsk a = shape_ask(dtype, kind, B, Hg, Wg, Cin, Cout);
+  const int64_t ws_plain = conv_route(a).ws_bytes;
+  a.prologue = true;
+  return std::max(ws_plain, conv_route(a).ws_bytes);
 }
 
 // out[0..3] = {BM, BN, ksplit, narrow-N path}; Hg x Wg is the GEMM grid (output grid for
 // the conv kinds, input grid for STC_CONVT_S2).
 extern "C" int stc_conv_fwd_plan(int dtype, int kind, int B, int Hg, int Wg, int Cin, int Cout, int32_t* out) {
   STC_REQUIRE(kind >= 0 && kind <= 3 && out, "stc_conv_fwd_plan: bad arguments");
-  const Geometry g = geometry(kind);
-  const int taps = g.taps_lg_tw == 2 ? 16 : 4;
-  const int M = B * Hg * Wg, K = taps * Cin;
-  if (use_smalln(dtype, Cout, K)) {
-    out[0] = 1; out[1] = Cout; out[2] = 1; out[3] = 1;
-    return 0;
-  }
-  if (bf16_path(dtype, kind, Cin, Cout)) {
-    int32_t po[5];
-    bf16_conv_query(kind, B, Hg, Wg, Cin, Cout, 0, nullptr, nullptr, nullptr, po);
-    for (int i = 0; i < 4; ++i) out[i] = po[i];
-    return 0;
-  }
-  const Plan pl = plan_for(dtype, M, Cout, K, g.nphase);
-  out[0] = pl.BM; out[1] = pl.BN; out[2] = pl.ksplit; out[3] = 0;
+  const ConvRoute r = conv_route(shape_ask(dtype, kind, B, Hg, Wg, Cin, Cout));
+  for (int i = 0; i < 4; ++i) out[i] = r.plan[i];
   return 0;
 }
 
-// Forward conv with fused BatchNorm output statistics and an optional forced plan
-// {tile config, ksplit} (bf16 LDS-DMA kernel only; tuning / tests).  stats_part: [chunks][Cout][4]
-// in stc_chan_stats format (merged by stc_bn_finalize).  plan_out[5] = {BM, BN, ksplit, narrow, cfg}.
+// Forward conv with fused BatchNorm output statistics and an optional forced plan (tuning /
+// tests).  stats_part: [chunks][Cout][4] in stc_chan_stats format (merged by stc_bn_finalize).
+// plan_out[5] = {BM, BN, ksplit, narrow, cfg}.
 extern "C" int stc_conv_fwd_query(int dtype, int kind, int B, int Hg, int Wg, int Cin, int Cout, int out_f32,
                                   const int32_t* force_plan, int64_t* workspace_bytes, int32_t* stats_chunks,
                                   int32_t* plan_out) {
   STC_REQUIRE(kind >= 0 && kind <= 3, "stc_conv_fwd_query: bad kind %d", kind);
-  const Geometry g = geometry(kind);
-  if (bf16_path(dtype, kind, Cin, Cout))
-    return bf16_conv_query(kind, B, Hg, Wg, Cin, Cout, out_f32, force_plan, workspace_bytes, stats_chunks, plan_out);
-  const long long P = (long long)B * Hg * Wg * (g.nphase == 4 ? 4 : 1);
-  if (workspace_bytes) *workspace_bytes = stc_conv_fwd_workspace(dtype, kind, B, Hg, Wg, Cin, Cout);
-  if (stats_chunks) *stats_chunks = stc_chan_stats_chunks(1, 1, (int)std::min<long long>(P, 1 << 30));
-  if (plan_out) {
-    int32_t o[4];
-    stc_conv_fwd_plan(dtype, kind, B, Hg, Wg, Cin, Cout, o);
-    for (int i = 0; i < 4; ++i) plan_out[i] = o[i];
-    plan_out[4] = -1;
-  }
+  ConvAsk a = shape_ask(dtype, kind, B, Hg, Wg, Cin, Cout);
+  a.out_f32 = out_f32 != 0;
+  a.stats = true;
+  a.force = force_plan;
+  const ConvRoute r = conv_route(a);
+  if (workspace_bytes) *workspace_bytes = r.ws_bytes;
+  if (stats_chunks) *stats_chunks = r.chunks;
+  if (plan_out)
+    for (int i = 0; i < 5; ++i) plan_out[i] = r.plan[i];
   return 0;
+}
+
+// ---- launches
+static int conv_fwd_checks(const ConvAsk& a, const ConvOps& o) {
+  STC_REQUIRE(a.dtype == STC_F32 || a.dtype == STC_BF16, "stc_conv_fwd: bad dtype %d", a.dtype);
+  STC_REQUIRE(a.kind >= 0 && a.kind <= 3, "stc_conv_fwd: bad kind %d", a.kind);
+  const int VEC = a.dtype == STC_F32 ? 4 : 8;
+  STC_REQUIRE(a.Cin >= VEC && a.Cin % VEC == 0, "stc_conv_fwd: Cin=%d must be a multiple of %d", a.Cin, VEC);
+  STC_REQUIRE(a.x.co % VEC == 0 && a.x.ps % VEC == 0 && a.x.cs == 1, "stc_conv_fwd: input view must be NHWC, 16-byte aligned channels");
+  STC_REQUIRE((o.pro_scale == nullptr) == (o.pro_shift == nullptr), "stc_conv_fwd: scale/shift must come together");
+  return 0;
+}
+
+// the kernel r names, for an ask that passed conv_fwd_checks
+static int conv_launch(const ConvAsk& a, const ConvRoute& r, const ConvOps& o) {
+  const int dtype = a.dtype, kind = a.kind, B = a.B, Cin = a.Cin, Cout = a.Cout;
+  const stc_view& x = a.x;
+  const stc_view& y = a.y;
+  if (B * r.GH * r.GW == 0 || Cout == 0) return 0;
+  switch (r.kernel) {
+    case STEM: case STEM_S1D: case HALO: case BF16_TILE:
+      return bf16_conv_fwd(a, r, o);
+    case BF16_NARROW:
+      return bf16_narrow_fwd(kind, B, x, Cin, o.w, Cout, y, o.bias, a.tanh, a.out_f32, o.ws, o.ws_bytes, o.st,
+                             r.narrow_force);
+    case CONV_NONE:
+      return fail(-1, "conv: no kernel for this call");
+    default:
+      break;
+  }
+  const Geometry g = geometry(kind);
+  const int K = (g.taps_lg_tw == 2 ? 16 : 4) * Cin;
+  ConvParams p{};
+  p.a = (const char*)x.p; p.a_bs = x.bs; p.a_rs = x.rs; p.a_ps = x.ps; p.a_co = x.co;
+  p.IH = x.H; p.IW = x.W;
+  p.cin = Cin; p.lg_tw = g.taps_lg_tw; p.in_stride = g.in_stride;
+  for (int i = 0; i < 4; ++i) { p.offy[i] = g.offy[i]; p.offx[i] = g.offx[i]; }
+  p.stepy = g.stepy; p.stepx = g.stepx;
+  p.sc = o.pro_scale; p.sh = o.pro_shift; p.pro_act = o.pro_act; p.slope = o.pro_slope;
+  p.GH = r.GH; p.GW = r.GW; p.M = B * r.GH * r.GW; p.N = Cout; p.K = K;
+  p.b = (const char*)o.w;
+  p.b_phase_stride = (long long)Cout * K;
+  p.c = (char*)y.p; p.c_bs = y.bs; p.c_rs = y.rs; p.c_ps = y.ps; p.c_co = y.co; p.c_cs = y.cs;
+  p.os = g.os;
+  for (int i = 0; i < 4; ++i) { p.oy0[i] = g.nphase == 4 ? (i >> 1) : 0; p.ox0[i] = g.nphase == 4 ? (i & 1) : 0; }
+  p.bias = o.bias; p.tanh_ = a.tanh; p.out_f32 = a.out_f32 || dtype == STC_F32;
+  p.nphase = g.nphase;
+  if (r.kernel == FP_TILE) {
+    const FpPlan& pl = r.fp;
+    p.ksplit = pl.ksplit; p.kchunk = pl.kchunk; p.mtiles = pl.mtiles; p.ntiles = pl.ntiles;
+    if (pl.ksplit > 1) {
+      STC_REQUIRE(o.ws && o.ws_bytes >= r.ws_bytes, "stc_conv_fwd: workspace %lld < %lld bytes",
+                  (long long)o.ws_bytes, (long long)r.ws_bytes);
+      p.ws = (float*)o.ws;
+    }
+    if (dtype == STC_F32) return launch_igemm<float>(pl, p, o.st);
+    return launch_igemm<bf16>(pl, p, o.st);
+  }
+  p.mtiles = 1; p.ntiles = 1; p.ksplit = 1; p.kchunk = K;
+  STC_REQUIRE(K % (dtype == STC_F32 ? 4 : 8) == 0, "stc_conv_fwd: K=%d", K);
+  if (r.kernel == NARROW_TILED) {
+    STC_DT(dtype, launch_narrow_tiled<T_>(kind, B, p, o.st));
+  } else {  // SMALLN
+    dim3 grid((unsigned)std::min(cdiv(p.M, 4), 4096), g.nphase);
+    const size_t lds = (size_t)Cout * K * (dtype == STC_F32 ? 4 : 2);
+    main_timer_begin(o.st);
+    STC_DT(dtype, hipLaunchKernelGGL(smalln_kernel<T_>, grid, dim3(256), lds, o.st, p));
+    main_timer_end(o.st);
+  }
+  STC_CHECK_LAUNCH();
+  return 0;
+}
+
+// checks, route, launch; statistics the kernel does not compute itself come from stc_chan_stats over its output.
+// stc_conv_fwd checks its arguments first; stc_conv_fwd_ex (kind checked) hands the bf16 family and the narrow tuning
+// hook to launchers that check their own, and runs these checks for the other routes only
+static int conv_fwd(const ConvAsk& a, ConvOps o, bool ex) {
+  if (!ex)
+    if (const int rc = conv_fwd_checks(a, o)) return rc;
+  const ConvRoute r = conv_route(a);
+  if (ex && !r.fused && !r.narrow_force)
+    if (const int rc = conv_fwd_checks(a, o)) return rc;
+  float* const stats_after = r.fused ? nullptr : o.stats;
+  if (!r.fused) o.stats = nullptr;
+  const int rc = conv_launch(a, r, o);
+  if (rc != 0 || stats_after == nullptr) return rc;
+  STC_REQUIRE(!a.out_f32 || a.dtype == STC_F32, "stc_conv_fwd_ex: stats of a non-activation output");
+  return stc_chan_stats(a.dtype, a.B, a.y, a.Cout, stats_after, o.stats_chunks, o.st);
 }
 
 extern "C" int stc_conv_fwd_ex(int dtype, int kind, int B, stc_view x, int Cin, const void* w_packed, int Cout,
@@ -755,19 +818,12 @@ extern "C" int stc_conv_fwd_ex(int dtype, int kind, int B, stc_view x, int Cin, 
                                int stats_chunks, const int32_t* force_plan, void* workspace, int64_t workspace_bytes,
                                void* stream) {
   STC_REQUIRE(kind >= 0 && kind <= 3, "stc_conv_fwd_ex: bad kind %d", kind);
-  hipStream_t st = (hipStream_t)stream;
-  if (bf16_path(dtype, kind, Cin, Cout) && !epi_tanh && bf16_conv_eligible(kind, B, x, Cin, Cout))
-    return bf16_conv_fwd(kind, B, x, Cin, w_packed, Cout, y, bias, epi_tanh, out_f32, stats_part, stats_chunks,
-                         force_plan, workspace, workspace_bytes, st);
-  if (force_plan && stats_part == nullptr && dtype == STC_BF16 && use_smalln(dtype, Cout, 16 * Cin) &&
-      bf16_narrow_eligible(kind, Cin, Cout))  // tuning hook: force_plan = {tile rows, 16-column blocks}
-    return bf16_narrow_fwd(kind, B, x, Cin, w_packed, Cout, y, bias, epi_tanh, out_f32, workspace, workspace_bytes, st,
-                           force_plan);
-  const int rc = stc_conv_fwd(dtype, kind, B, x, Cin, nullptr, nullptr, 0, 0.f, w_packed, Cout, y, bias, epi_tanh,
-                              out_f32, workspace, workspace_bytes, stream);
-  if (rc != 0 || stats_part == nullptr) return rc;
-  STC_REQUIRE(!out_f32 || dtype == STC_F32, "stc_conv_fwd_ex: stats of a non-activation output");
-  return stc_chan_stats(dtype, B, y, Cout, stats_part, stats_chunks, stream);
+  ConvAsk a = conv_ask(dtype, kind, B, x, Cin, Cout, y);
+  a.tanh = epi_tanh != 0; a.out_f32 = out_f32 != 0; a.stats = stats_part != nullptr; a.force = force_plan;
+  ConvOps o{};
+  o.w = w_packed; o.bias = bias; o.stats = stats_part; o.stats_chunks = stats_chunks;
+  o.ws = workspace; o.ws_bytes = workspace_bytes; o.st = (hipStream_t)stream;
+  return conv_fwd(a, o, true);
 }
 
 // conv + BatchNorm (train mode) + activation as one call: stc_conv_fwd_ex with the batch statistics, stc_bn_finalize,
@@ -795,136 +851,65 @@ extern "C" int stc_conv_fwd(int dtype, int kind, int B, stc_view x, int Cin,
                             const void* w_packed, int Cout, stc_view y,
                             const float* bias, int epi_tanh, int out_f32,
                             void* workspace, int64_t workspace_bytes, void* stream) {
-  STC_REQUIRE(dtype == STC_F32 || dtype == STC_BF16, "stc_conv_fwd: bad dtype %d", dtype);
-  STC_REQUIRE(kind >= 0 && kind <= 3, "stc_conv_fwd: bad kind %d", kind);
-  const int VEC = dtype == STC_F32 ? 4 : 8;
-  const int BK = dtype == STC_F32 ? 32 : 64;
-  STC_REQUIRE(Cin >= VEC && Cin % VEC == 0, "stc_conv_fwd: Cin=%d must be a multiple of %d", Cin, VEC);
-  STC_REQUIRE(x.co % VEC == 0 && x.ps % VEC == 0 && x.cs == 1, "stc_conv_fwd: input view must be NHWC, 16-byte aligned channels");
-  const Geometry g = geometry(kind);
-  const int taps = g.taps_lg_tw == 2 ? 16 : 4;
-  const int K = taps * Cin;
-  (void)BK;
-  // GEMM grid: conv kinds -> output grid; convT -> input grid
-  int GH, GW;
-  if (kind == STC_CONVT_S2) { GH = x.H; GW = x.W; }
-  else { GH = y.H; GW = y.W; }
-  ConvParams p{};
-  p.a = (const char*)x.p; p.a_bs = x.bs; p.a_rs = x.rs; p.a_ps = x.ps; p.a_co = x.co;
-  p.IH = x.H; p.IW = x.W;
-  p.cin = Cin; p.lg_tw = g.taps_lg_tw; p.in_stride = g.in_stride;
-  for (int i = 0; i < 4; ++i) { p.offy[i] = g.offy[i]; p.offx[i] = g.offx[i]; }
-  p.stepy = g.stepy; p.stepx = g.stepx;
-  p.sc = pro_scale; p.sh = pro_shift; p.pro_act = pro_act; p.slope = pro_slope;
-  STC_REQUIRE((pro_scale == nullptr) == (pro_shift == nullptr), "stc_conv_fwd: scale/shift must come together");
-  p.GH = GH; p.GW = GW; p.M = B * GH * GW; p.N = Cout; p.K = K;
-  p.b = (const char*)w_packed;
-  p.b_phase_stride = (long long)Cout * K;
-  p.c = (char*)y.p; p.c_bs = y.bs; p.c_rs = y.rs; p.c_ps = y.ps; p.c_co = y.co; p.c_cs = y.cs;
-  p.os = g.os;
-  for (int i = 0; i < 4; ++i) { p.oy0[i] = g.nphase == 4 ? (i >> 1) : 0; p.ox0[i] = g.nphase == 4 ? (i & 1) : 0; }
-  p.bias = bias; p.tanh_ = epi_tanh; p.out_f32 = out_f32 || dtype == STC_F32;
-  p.nphase = g.nphase;
-  if (p.M == 0 || Cout == 0) return 0;
-  hipStream_t st0 = (hipStream_t)stream;
-  if (use_smalln(dtype, Cout, K)) {
-    if (dtype == STC_BF16 && p.sc == nullptr && pro_act == 0 && bf16_narrow_eligible(kind, Cin, Cout))
-      return bf16_narrow_fwd(kind, B, x, Cin, w_packed, Cout, y, bias, epi_tanh, out_f32, workspace, workspace_bytes,
-                             st0);
-    p.mtiles = 1; p.ntiles = 1; p.ksplit = 1; p.kchunk = K;
-    const int esz = dtype == STC_F32 ? 4 : 2;
-    STC_REQUIRE(K % VEC == 0, "stc_conv_fwd: K=%d", K);
-    const bool tiled = dtype == STC_F32 ? launch_narrow_tiled<float>(kind, B, p, st0)
-                                        : launch_narrow_tiled<bf16>(kind, B, p, st0);
-    if (tiled) {
-      STC_CHECK_LAUNCH();
-      return 0;
-    }
-    dim3 grid((unsigned)std::min(cdiv(p.M, 4), 4096), g.nphase);
-    const size_t lds = (size_t)Cout * K * esz;
-    main_timer_begin(st0);
-    if (dtype == STC_F32) hipLaunchKernelGGL(smalln_kernel<float>, grid, dim3(256), lds, st0, p);
-    else hipLaunchKernelGGL(smalln_kernel<bf16>, grid, dim3(256), lds, st0, p);
-    main_timer_end(st0);
-    STC_CHECK_LAUNCH();
-    return 0;
-  }
-  if (dtype == STC_BF16 && p.sc == nullptr && pro_act == 0 && !epi_tanh && bf16_conv_eligible(kind, B, x, Cin, Cout))
-    return bf16_conv_fwd(kind, B, x, Cin, w_packed, Cout, y, bias, epi_tanh, out_f32, nullptr, 0, nullptr,
-                         workspace, workspace_bytes, st0);
-  const Plan pl = plan_for(dtype, p.M, Cout, K, g.nphase);
-  p.ksplit = pl.ksplit; p.kchunk = pl.kchunk; p.mtiles = pl.mtiles; p.ntiles = pl.ntiles;
-  if (pl.ksplit > 1) {
-    const int64_t need = (int64_t)g.nphase * pl.ksplit * (int64_t)p.M * Cout * 4;
-    STC_REQUIRE(workspace && workspace_bytes >= need, "stc_conv_fwd: workspace %lld < %lld bytes",
-                (long long)workspace_bytes, (long long)need);
-    p.ws = (float*)workspace;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STC_F32) return launch_igemm<float>(pl, p, st);
-  return launch_igemm<bf16>(pl, p, st);
+  ConvAsk a = conv_ask(dtype, kind, B, x, Cin, Cout, y);
+  a.prologue = pro_scale != nullptr || pro_act != 0; a.tanh = epi_tanh != 0; a.out_f32 = out_f32 != 0;
+  ConvOps o{};
+  o.w = w_packed; o.bias = bias;
+  o.pro_scale = pro_scale; o.pro_shift = pro_shift; o.pro_act = pro_act; o.pro_slope = pro_slope;
+  o.ws = workspace; o.ws_bytes = workspace_bytes; o.st = (hipStream_t)stream;
+  return conv_fwd(a, o, false);
 }
 
 // ---- input-gradient conv + fused BN-backward reduction
-static bool bnb_fused_path(int dtype, int kind, int B, const stc_view& dy, int Cin, int Cout, const stc_view& out) {
-  const bool vec = out.cs == 1 && out.co % 8 == 0 && out.ps % 8 == 0 && out.rs % 8 == 0 && out.bs % 8 == 0 &&
-                   ((uintptr_t)out.p & 15) == 0;
-  return bf16_path(dtype, kind, Cin, Cout) && vec && bf16_conv_eligible(kind, B, dy, Cin, Cout);
-}
-
-namespace stc {
-int stem_bnb_chunks(int kind, int B, int Hg, int Wg, int Cin, int Cout);
-int bf16_bnb_chunks(int kind, int B, const stc_view& x, int Cin, int Cout, const stc_view& y, bool g_other);
+static ConvAsk bwd_bn_ask(int dtype, int kind, int B, const stc_view& dy, int Cin, int Cout, const stc_view& out,
+                          const stc_bnb_fuse* bnb) {
+  ConvAsk a = conv_ask(dtype, kind, B, dy, Cin, Cout, out);
+  a.bnb = bnb;
+  return a;
 }
 
 // the part2 chunk count of stc_conv_bwd_bn for these exact views (the kernel route depends on the layout)
-static int bwd_bn_chunks_of(int dtype, int kind, int B, const stc_view& dy, int Cin, int Cout, const stc_view& out,
-                            const stc_bnb_fuse& bnb) {
-  if (bnb_fused_path(dtype, kind, B, dy, Cin, Cout, out))
-    return bf16_bnb_chunks(kind, B, dy, Cin, Cout, out, bnb.g_other.p != nullptr);
-  return stc_chan_stats_chunks(B, bnb.x.H, bnb.x.W);
-}
-
 extern "C" int stc_conv_bwd_bn_chunks_ex(int dtype, int kind, int B, stc_view dy, int Cin, int Cout, stc_view out,
                                          const stc_bnb_fuse* bnb) {
   if (!bnb || kind < 0 || kind > 3) return fail(-1, "stc_conv_bwd_bn_chunks_ex: bad arguments"), 0;
-  return bwd_bn_chunks_of(dtype, kind, B, dy, Cin, Cout, out, *bnb);
+  return conv_route(bwd_bn_ask(dtype, kind, B, dy, Cin, Cout, out, bnb)).chunks;
 }
 
-// (shape-only form: assumes dense 16-byte NHWC views at channel offset 0 and no second gradient for the 31 x 31
-// logits-layer input gradient -- stc_conv_bwd_bn_chunks_ex answers for the actual views)
+// (shape-only form: the views of shape_ask, the BN input dense over xH x xW -- stc_conv_bwd_bn_chunks_ex answers for
+// the actual views)
 extern "C" int stc_conv_bwd_bn_chunks(int dtype, int kind, int B, int Hg, int Wg, int Cin, int Cout, int xH, int xW) {
-  if (bf16_path(dtype, kind, Cin, Cout)) {
-    if (const int sn = stem_bnb_chunks(kind, B, Hg, Wg, Cin, Cout)) return sn;  // (the streaming Cin = 8 kernel)
-    int32_t nch = 0;
-    bf16_conv_query(kind, B, Hg, Wg, Cin, Cout, 0, nullptr, nullptr, &nch, nullptr);
-    return nch;  // (NHWC 16-byte aligned views assumed: the fused path)
-  }
-  return stc_chan_stats_chunks(B, xH, xW);
+  stc_bnb_fuse f{};
+  f.x = dense_view(xH, xW, Cout);
+  f.C = Cout;
+  ConvAsk a = shape_ask(dtype, kind, B, Hg, Wg, Cin, Cout);
+  a.bnb = &f;
+  return conv_route(a).chunks;
 }
 
 extern "C" int stc_conv_bwd_bn(int dtype, int kind, int B, stc_view dy, int Cin, const void* w_packed, int Cout,
                                stc_view out, const stc_bnb_fuse* bnb, float* part2, int nchunks, void* workspace,
                                int64_t workspace_bytes, void* stream) {
   STC_REQUIRE(bnb && part2, "stc_conv_bwd_bn: bnb and part2 required");
-  hipStream_t st = (hipStream_t)stream;
-  if (bnb_fused_path(dtype, kind, B, dy, Cin, Cout, out)) {
-    const int need = bwd_bn_chunks_of(dtype, kind, B, dy, Cin, Cout, out, *bnb);
-    STC_REQUIRE(nchunks == need, "stc_conv_bwd_bn: %d chunks != %d (use stc_conv_bwd_bn_chunks_ex)", nchunks, need);
-    return bf16_conv_fwd(kind, B, dy, Cin, w_packed, Cout, out, nullptr, 0, 0, nullptr, need, nullptr, workspace,
-                         workspace_bytes, st, bnb, part2);
+  ConvAsk a = bwd_bn_ask(dtype, kind, B, dy, Cin, Cout, out, bnb);
+  const ConvRoute r = conv_route(a);
+  ConvOps o{};
+  o.w = w_packed; o.ws = workspace; o.ws_bytes = workspace_bytes; o.st = (hipStream_t)stream;
+  if (r.fused) {
+    STC_REQUIRE(nchunks == r.chunks, "stc_conv_bwd_bn: %d chunks != %d (use stc_conv_bwd_bn_chunks_ex)", nchunks, r.chunks);
+    o.part2 = part2; o.stats_chunks = r.chunks;
+    return bf16_conv_fwd(a, r, o);
   }
-  int rc = stc_conv_fwd(dtype, kind, B, dy, Cin, nullptr, nullptr, 0, 0.f, w_packed, Cout, out, nullptr, 0, 0,
-                        workspace, workspace_bytes, stream);
+  a.bnb = nullptr;  // the plain conv (r is its route), then the reduction over its output
+  int rc = conv_fwd_checks(a, o);
+  if (rc == 0) rc = conv_launch(a, r, o);
   if (rc) return rc;
   stc_view g1 = out;  // this conv's output, at the BN channels, over the BN extent
   g1.co += bnb->ch_off;
   g1.H = bnb->x.H;
   g1.W = bnb->x.W;
-  const int need = stc_chan_stats_chunks(B, bnb->x.H, bnb->x.W);
-  STC_REQUIRE(nchunks == need, "stc_conv_bwd_bn: %d chunks != %d (use stc_conv_bwd_bn_chunks_ex)", nchunks, need);
+  STC_REQUIRE(nchunks == r.chunks, "stc_conv_bwd_bn: %d chunks != %d (use stc_conv_bwd_bn_chunks_ex)", nchunks, r.chunks);
   return stc_bn_bwd_reduce(dtype, B, bnb->x, bnb->C, bnb->scale, bnb->shift, bnb->mean, bnb->rstd, g1, bnb->slope_self,
-                           bnb->g_other, bnb->slope_other, part2, need, stream);
+                           bnb->g_other, bnb->slope_other, part2, r.chunks, stream);
 }
 
 // stc_conv_bwd_bn followed by its stc_bn_bwd_apply (the conv output at the BN channels over the BN extent as the
@@ -944,44 +929,71 @@ extern "C" int stc_conv_bwd_bn_apply(int dtype, int kind, int B, stc_view dy, in
                           bnb->slope_self, bnb->g_other, bnb->slope_other, part2, nchunks, dx, dgamma, dbeta, stream);
 }
 
-// ---- input-gradient conv + activation backward (layers without BatchNorm)
-namespace stc {
-bool bf16_conv_bwd_act_ok(int kind, int B, const stc_view& dy, int Cin, int Cout, const stc_view& out, const stc_view& x,
-                          const stc_view* g_other);
-}  // namespace stc
+// ---- input-gradient conv + activation backward (layers without BatchNorm): the halo kernels' BN-backward epilogue
+// with no table (f: the activation's input and the second gradient, filled here)
+static ConvAsk bwd_act_ask(int dtype, int kind, int B, const stc_view& dy, int Cin, int Cout, const stc_view& out,
+                           const stc_view& x, const stc_view& g_other, stc_bnb_fuse& f) {
+  f.x = x;
+  f.g_other = g_other;
+  f.C = Cout;
+  f.ch_off = 0;
+  ConvAsk a = conv_ask(dtype, kind, B, dy, Cin, Cout, out);
+  a.bnb = &f;
+  a.bnb_act = true;
+  return a;
+}
+
 extern "C" int stc_conv_bwd_act_ok(int dtype, int kind, int B, stc_view dy, int Cin, int Cout, stc_view out, stc_view x,
                                    stc_view g_other) {
-  if (kind < 0 || kind > 3 || !bf16_path(dtype, kind, Cin, Cout)) return 0;
-  return bf16_conv_bwd_act_ok(kind, B, dy, Cin, Cout, out, x, &g_other) ? 1 : 0;
+  if (kind < 0 || kind > 3) return 0;
+  stc_bnb_fuse f{};
+  return conv_route(bwd_act_ask(dtype, kind, B, dy, Cin, Cout, out, x, g_other, f)).kernel == HALO ? 1 : 0;
 }
 
 extern "C" int stc_conv_bwd_act(int dtype, int kind, int B, stc_view dy, int Cin, const void* w_packed, int Cout,
                                 stc_view out, stc_view x, float slope_self, stc_view g_other, float slope_other,
                                 void* stream) {
-  STC_REQUIRE(stc_conv_bwd_act_ok(dtype, kind, B, dy, Cin, Cout, out, x, g_other),
-              "stc_conv_bwd_act: no fused activation backward for this shape / view (check stc_conv_bwd_act_ok)");
   stc_bnb_fuse f{};
-  f.x = x;
-  f.g_other = g_other;
   f.slope_self = slope_self;
   f.slope_other = slope_other;
-  f.C = Cout;
-  f.ch_off = 0;
-  return bf16_conv_fwd(kind, B, dy, Cin, w_packed, Cout, out, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0,
-                       (hipStream_t)stream, &f, nullptr, nullptr, 0, 0.f, 0.f, 1);
+  const ConvAsk a = bwd_act_ask(dtype, kind, B, dy, Cin, Cout, out, x, g_other, f);
+  ConvRoute r{};
+  if (kind >= 0 && kind <= 3) r = conv_route(a);
+  STC_REQUIRE(r.kernel == HALO,
+              "stc_conv_bwd_act: no fused activation backward for this shape / view (check stc_conv_bwd_act_ok)");
+  ConvOps o{};
+  o.w = w_packed; o.st = (hipStream_t)stream;
+  return bf16_conv_fwd(a, r, o);
 }
 
-// ---- conv + activation epilogue (layers without BatchNorm)
+// ---- conv + activation epilogue (layers without BatchNorm): the stem kernel, or the bf16 tile as one launch
+static ConvAsk fwd_act_ask(int dtype, int kind, int B, const stc_view& x, int Cin, int Cout, const stc_view& y1,
+                           const stc_view& y2) {
+  ConvAsk a = conv_ask(dtype, kind, B, x, Cin, Cout, y1);
+  a.act_n = y2.p ? 2 : 1;
+  a.act2 = &y2;
+  return a;
+}
+static bool fwd_act_ok(const ConvRoute& r) {
+  return r.kernel == STEM || (r.kernel == BF16_TILE && r.bf.pl.ksplit == 1);
+}
+
 extern "C" int stc_conv_fwd_act_ok(int dtype, int kind, int B, stc_view x, int Cin, int Cout, stc_view y1, stc_view y2) {
-  if (kind < 0 || kind > 3 || !bf16_path(dtype, kind, Cin, Cout)) return 0;
-  return bf16_conv_act_ok(kind, B, x, Cin, Cout, y1, y2.p ? &y2 : nullptr) ? 1 : 0;
+  if (kind < 0 || kind > 3) return 0;
+  return fwd_act_ok(conv_route(fwd_act_ask(dtype, kind, B, x, Cin, Cout, y1, y2))) ? 1 : 0;
 }
 
 extern "C" int stc_conv_fwd_act(int dtype, int kind, int B, stc_view x, int Cin, const void* w_packed, int Cout,
                                 stc_view y1, float slope1, stc_view y2, float slope2, const float* bias,
                                 void* workspace, int64_t workspace_bytes, void* stream) {
-  STC_REQUIRE(stc_conv_fwd_act_ok(dtype, kind, B, x, Cin, Cout, y1, y2),
+  const ConvAsk a = fwd_act_ask(dtype, kind, B, x, Cin, Cout, y1, y2);
+  ConvRoute r{};
+  if (kind >= 0 && kind <= 3) r = conv_route(a);
+  STC_REQUIRE(fwd_act_ok(r),
               "stc_conv_fwd_act: no activation epilogue for this shape (check stc_conv_fwd_act_ok)");
-  return bf16_conv_fwd(kind, B, x, Cin, w_packed, Cout, y1, bias, 0, 0, nullptr, 0, nullptr, workspace, workspace_bytes,
-                       (hipStream_t)stream, nullptr, nullptr, &y2, y2.p ? 2 : 1, slope1, slope2);
+  ConvOps o{};
+  o.w = w_packed; o.bias = bias; o.act_s1 = slope1; o.act_s2 = slope2;
+  o.ws = workspace; o.ws_bytes = workspace_bytes; o.st = (hipStream_t)stream;
+  return bf16_conv_fwd(a, r, o);
 }
+

@@ -22,6 +22,7 @@
 #include <tuple>
 #include <unordered_map>
 
+#include "conv_route.hpp"
 #include "igemm_bf16.hpp"
 
 namespace stc {
@@ -514,11 +515,6 @@ __global__ void __launch_bounds__(256) splitk_reduce_wide_kernel(const GParams p
 }
 
 // ------------------------------------------------------------------------- host
-struct BPlan {
-  int cfg;  // index into the tile table
-  int BM, BN, ksplit, kchunk, mtiles, ntiles;
-};
-
 struct TileCfg {
   int BM, BN, WM, WN, NST, BK;
 };
@@ -653,17 +649,6 @@ using namespace stc;
 
 namespace stc {
 
-struct Bf16Problem {
-  int M, N, K, nphase;
-  BPlan pl;
-  bool vec_out;
-  int64_t ws_bytes;
-  int stats_chunks;
-  int reduce_rows;
-  bool wide;      // split-K reduction by splitk_reduce_wide_kernel (a chunk per row)
-  bool inlaunch;  // split-K combined in the launch (GParams::slab / tickets): the tile statistics of one launch
-};
-
 // Ticket counters of the in-launch split-K.  A region belongs to one (device, stream, capture): launches on one stream
 // run one after another and every launch leaves its counters zero, so eager launches on a stream share its region; a
 // launch made while the stream is being captured gets a region of that capture (the graph's replays may run beside
@@ -701,8 +686,8 @@ static unsigned* splitk_tickets(hipStream_t st, int tiles) {
   return pool[dev] + (size_t)used[dev]++ * kTicketRegion;
 }
 
-// Shared planning for query and launch.
-static Bf16Problem bf16_problem(int M, int N, int K, int nphase, const int32_t* force, bool vec_out) {
+// The tile problem of a shape: plan, workspace, chunk count (conv_route carries it to the launch).
+Bf16Problem bf16_problem(int M, int N, int K, int nphase, const int32_t* force, bool vec_out) {
   Bf16Problem pr{};
   pr.M = M; pr.N = N; pr.K = K; pr.nphase = nphase;
   pr.pl = bf16_plan(M, N, K, nphase, force ? force[0] : -1, force ? force[1] : 0, vec_out);
@@ -728,25 +713,11 @@ static Bf16Problem bf16_problem(int M, int N, int K, int nphase, const int32_t* 
   return pr;
 }
 
-bool bf16_igemm_eligible(int N, int K) { return N >= 16 && N % 8 == 0 && N <= 2048 && K % 8 == 0; }
+static bool bf16_igemm_eligible(int N, int K) { return N >= 16 && N % 8 == 0 && N <= 2048 && K % 8 == 0; }
 
-int bf16_igemm_query(int M, int N, int K, int nphase, const int32_t* force, int64_t* ws_bytes, int32_t* stats_chunks,
-                     int32_t* plan_out) {
-  Bf16Problem pr = bf16_problem(M, N, K, nphase, force, true);
-  if (ws_bytes) *ws_bytes = pr.ws_bytes;
-  if (stats_chunks) *stats_chunks = pr.stats_chunks;
-  if (plan_out) {
-    plan_out[0] = pr.pl.BM; plan_out[1] = pr.pl.BN; plan_out[2] = pr.pl.ksplit; plan_out[3] = 0;
-    plan_out[4] = pr.pl.cfg;
-  }
-  return 0;
-}
-
-// p: filled by the caller (geometry, operands, output); returns 0 or error.
-
-int bf16_igemm_launch(GParams& p, const int32_t* force, void* ws, int64_t ws_bytes, float* stats, int stats_chunks,
+// p: filled by the caller (geometry, operands, output); pr: bf16_problem of p's shape; returns 0 or error.
+int bf16_igemm_launch(GParams& p, const Bf16Problem& pr, void* ws, int64_t ws_bytes, float* stats, int stats_chunks,
                       hipStream_t st) {
-  Bf16Problem pr = bf16_problem(p.M, p.N, p.K, p.nphase, force, p.vec_out != 0);
   const BPlan& pl = pr.pl;
   p.ksplit = pl.ksplit; p.kchunk = pl.kchunk; p.mtiles = pl.mtiles; p.ntiles = pl.ntiles;
   p.stats = nullptr;
@@ -854,11 +825,10 @@ int bf16_igemm_launch(GParams& p, const int32_t* force, void* ws, int64_t ws_byt
   return 0;
 }
 
-// ---- conv-level wrappers (geometry -> GParams), used by stc_conv_fwd_query / stc_conv_fwd_ex
-static bool vec_out_ok(int B, const stc_view& y, int Cout, int out_f32) {
+// ---- conv level: the predicates conv_route asks, and the launcher of the bf16 GParams kernels
+bool vec_out_ok(int B, const stc_view& y, int Cout, int out_f32) {
   const long long extent = (long long)(B - 1) * y.bs + (long long)(y.H - 1) * y.rs + (long long)(y.W - 1) * y.ps + y.co + Cout;
-  return !out_f32 && y.cs == 1 && y.co % 8 == 0 && y.ps % 8 == 0 && y.rs % 8 == 0 && y.bs % 8 == 0 &&
-         ((uintptr_t)y.p & 15) == 0 && extent < (1ll << 31);
+  return !out_f32 && vec16_view(y) && extent < (1ll << 31);
 }
 
 bool bf16_conv_eligible(int kind, int B, const stc_view& x, int Cin, int Cout) {
@@ -870,57 +840,16 @@ bool bf16_conv_eligible(int kind, int B, const stc_view& x, int Cin, int Cout) {
          a_bytes < (1ll << 31) && b_bytes < (1ll << 31);
 }
 
-// The conv-s2 halo kernel (halo_bf16.hip): plan config HALO_CFG.  force_plan: NULL / {-1, .}: automatic (the
-// halo kernel where eligible), {HALO_CFG, .}: the halo kernel (an error where it is not eligible), {-2, .}: the
-// automatic im2col plan (A/B), {cfg >= 0, .}: that im2col tile.
-constexpr int HALO_CFG = 100;
-bool halo_geometry_ok(int kind, int B, int GH, int GW, int Cin, int Cout);
-bool halo_auto(int kind, int B, int GH, int GW, int Cin, int Cout);
-bool halo_eligible(int kind, int B, const stc_view& x, int Cin, int Cout, const stc_view& y);
-int halo_chunks(int kind, int B, int GH, int GW);
-int halo_launch(GParams& p, hipStream_t st, int shape);
-int halo_plan_bn(int kind, int B, int GH, int GW, int Cout, int shape);
-// the Cin = 8 first layers with the activation epilogue (stem_bf16.hip)
-bool stem_eligible(int kind, int B, const stc_view& x, int Cin, int Cout, const stc_view& y, bool bnb);
-int stem_launch(GParams& p, hipStream_t st);
-bool stem_s1d_eligible(int kind, int B, const stc_view& dy, int Cin, int Cout, const stc_view& y);
-int stem_s1d_launch(GParams& p, hipStream_t st);
-int stem_bnb_chunks(int kind, int B, int Hg, int Wg, int Cin, int Cout);
-static bool halo_plan(const int32_t* force, int kind, int B, int GH, int GW, int Cin, int Cout) {
-  if (force && force[0] == HALO_CFG) return halo_geometry_ok(kind, B, GH, GW, Cin, Cout);
-  return (!force || force[0] == -1) && halo_auto(kind, B, GH, GW, Cin, Cout);
-}
-
-int bf16_conv_query(int kind, int B, int Hg, int Wg, int Cin, int Cout, int out_f32, const int32_t* force,
-                    int64_t* ws_bytes, int32_t* stats_chunks, int32_t* plan_out) {
-  if (!out_f32 && halo_plan(force, kind, B, Hg, Wg, Cin, Cout)) {
-    if (ws_bytes) *ws_bytes = 0;
-    if (stats_chunks) *stats_chunks = halo_chunks(kind, B, Hg, Wg);
-    if (plan_out) {
-      plan_out[0] = 256; plan_out[1] = halo_plan_bn(kind, B, Hg, Wg, Cout, force && force[0] == HALO_CFG ? force[1] : 0); plan_out[2] = 1; plan_out[3] = 0;
-      plan_out[4] = HALO_CFG;
-    }
-    return 0;
-  }
-  if (force && force[0] == HALO_CFG) force = nullptr;
-  const Geometry g = geometry(kind);
-  const int taps = g.taps_lg_tw == 2 ? 16 : 4;
-  Bf16Problem pr = bf16_problem(B * Hg * Wg, Cout, taps * Cin, g.nphase, force, !out_f32);
-  if (ws_bytes) *ws_bytes = pr.ws_bytes;
-  if (stats_chunks) *stats_chunks = pr.stats_chunks;
-  if (plan_out) {
-    plan_out[0] = pr.pl.BM; plan_out[1] = pr.pl.BN; plan_out[2] = pr.pl.ksplit; plan_out[3] = 0;
-    plan_out[4] = pr.pl.cfg;
-  }
-  return 0;
-}
-
-int bf16_conv_fwd(int kind, int B, stc_view x, int Cin, const void* w_packed, int Cout, stc_view y,
-                  const float* bias, int epi_tanh, int out_f32, float* stats, int stats_chunks,
-                  const int32_t* force, void* ws, int64_t ws_bytes, hipStream_t st,
-                  const stc_bnb_fuse* bnb = nullptr, float* part2 = nullptr,
-                  const stc_view* act2 = nullptr, int act_n = 0, float act_s1 = 0.f, float act_s2 = 0.f,
-                  int bnb_act = 0) {
+// geometry -> GParams, then the kernel r names: the streaming stem kernels (stem_bf16.hip), the halo kernels
+// (halo_bf16.hip) or the im2col tile
+int bf16_conv_fwd(const ConvAsk& a, const ConvRoute& r, const ConvOps& o) {
+  const int kind = a.kind, B = a.B, Cin = a.Cin, Cout = a.Cout;
+  const stc_view& x = a.x;
+  const stc_view& y = a.y;
+  const stc_bnb_fuse* bnb = a.bnb;
+  float* const stats = o.stats;
+  float* const part2 = o.part2;
+  hipStream_t st = o.st;
   const Geometry g = geometry(kind);
   const int taps = g.taps_lg_tw == 2 ? 16 : 4;
   GParams p{};
@@ -931,31 +860,30 @@ int bf16_conv_fwd(int kind, int B, stc_view x, int Cin, const void* w_packed, in
   p.cin = Cin; p.lg_tw = g.taps_lg_tw; p.in_stride = g.in_stride;
   for (int i = 0; i < 4; ++i) { p.offy[i] = g.offy[i]; p.offx[i] = g.offx[i]; }
   p.stepy = g.stepy; p.stepx = g.stepx;
-  if (kind == STC_CONVT_S2) { p.GH = x.H; p.GW = x.W; }
-  else { p.GH = y.H; p.GW = y.W; }
+  p.GH = r.GH; p.GW = r.GW;
   p.M = B * p.GH * p.GW; p.N = Cout; p.K = taps * Cin;
   STC_REQUIRE(p.M < (1 << 24), "bf16 conv: M = %d pixels per phase (>= 2^24)", p.M);
   p.inv_ghw = 1.0f / (float)(p.GH * p.GW);
   p.inv_gw = 1.0f / (float)p.GW;
-  p.b = (const char*)w_packed;
+  p.b = (const char*)o.w;
   p.b_phase_stride = Cout * p.K;
   p.b_bytes = (unsigned)((long long)g.nphase * p.b_phase_stride * 2);
   p.c = (char*)y.p; p.c_bs = y.bs; p.c_rs = y.rs; p.c_ps = y.ps; p.c_co = y.co; p.c_cs = y.cs;
   p.os = g.os;
   for (int i = 0; i < 4; ++i) { p.oy0[i] = g.nphase == 4 ? (i >> 1) : 0; p.ox0[i] = g.nphase == 4 ? (i & 1) : 0; }
-  p.bias = bias; p.tanh_ = epi_tanh; p.out_f32 = out_f32;
-  p.vec_out = vec_out_ok(B, y, Cout, out_f32) && Cout % 8 == 0 ? 1 : 0;
+  p.bias = o.bias; p.tanh_ = a.tanh; p.out_f32 = a.out_f32;
+  p.vec_out = r.vec_out ? 1 : 0;
   p.nphase = g.nphase;
   if (p.M == 0 || Cout == 0) return 0;
-  STC_REQUIRE(!epi_tanh, "bf16 conv: the MFMA tile kernel has no tanh epilogue");
-  if (!p.vec_out) STC_REQUIRE(!stats || out_f32 == 0, "bf16 conv: stats need a bf16 output");
+  STC_REQUIRE(!a.tanh, "bf16 conv: the MFMA tile kernel has no tanh epilogue");
+  if (!p.vec_out) STC_REQUIRE(!stats || a.out_f32 == 0, "bf16 conv: stats need a bf16 output");
   if (bnb) {
-    STC_REQUIRE(p.vec_out && (part2 || bnb_act) && !stats, "bf16 conv: fused BN backward needs a 16-byte NHWC bf16 output");
+    STC_REQUIRE(p.vec_out && (part2 || a.bnb_act) && !stats, "bf16 conv: fused BN backward needs a 16-byte NHWC bf16 output");
     STC_REQUIRE(bnb->C % 8 == 0 && bnb->ch_off % 8 == 0 && bnb->x.cs == 1 && bnb->x.co % 8 == 0 && bnb->x.ps % 8 == 0 &&
                     (!bnb->g_other.p || (bnb->g_other.cs == 1 && bnb->g_other.co % 8 == 0 && bnb->g_other.ps % 8 == 0)) &&
-                    (bnb_act || (bnb->scale && bnb->shift && bnb->mean && bnb->rstd)),
+                    (a.bnb_act || (bnb->scale && bnb->shift && bnb->mean && bnb->rstd)),
                 "bf16 conv: bad fused BN-backward arguments");
-    p.bnb_act = bnb_act;
+    p.bnb_act = a.bnb_act;
     p.part2 = part2;
     p.bx = (const char*)bnb->x.p; p.bx_bs = bnb->x.bs; p.bx_rs = bnb->x.rs; p.bx_ps = bnb->x.ps; p.bx_co = bnb->x.co;
     p.bxH = bnb->x.H; p.bxW = bnb->x.W;
@@ -965,80 +893,35 @@ int bf16_conv_fwd(int kind, int B, stc_view x, int Cin, const void* w_packed, in
     p.bs_self = bnb->slope_self; p.bs_other = bnb->slope_other;
     p.bC = bnb->C; p.bch_off = bnb->ch_off;
   }
-  if (act_n) {
-    STC_REQUIRE(p.vec_out && !bnb && !stats && (act_n == 1 || (act2 && act2->p)),
+  if (a.act_n) {
+    STC_REQUIRE(p.vec_out && !bnb && !stats && (a.act_n == 1 || (a.act2 && a.act2->p)),
                 "bf16 conv: activation epilogue needs a 16-byte NHWC bf16 output and no statistics");
-    p.act_n = act_n; p.act_s1 = act_s1; p.act_s2 = act_s2;
-    if (act_n == 2) {
-      p.c2 = (char*)act2->p; p.c2_bs = act2->bs; p.c2_rs = act2->rs; p.c2_ps = act2->ps; p.c2_co = act2->co;
+    p.act_n = a.act_n; p.act_s1 = o.act_s1; p.act_s2 = o.act_s2;
+    if (a.act_n == 2) {
+      p.c2 = (char*)a.act2->p; p.c2_bs = a.act2->bs; p.c2_rs = a.act2->rs; p.c2_ps = a.act2->ps; p.c2_co = a.act2->co;
     }
   }
-  if (bnb_act) {  // (the halo kernels' epilogue only: stc_conv_bwd_act_ok)
-    STC_REQUIRE(!force && !part2 && bnb->C == Cout && bnb->ch_off == 0 && halo_plan(nullptr, kind, B, p.GH, p.GW, Cin, Cout) &&
-                    halo_eligible(kind, B, x, Cin, Cout, y),
+  if (a.bnb_act)  // (the halo kernels' epilogue only: stc_conv_bwd_act_ok)
+    STC_REQUIRE(!part2 && r.kernel == HALO,
                 "bf16 conv: no fused activation backward for this shape / view (check stc_conv_bwd_act_ok)");
-    p.ws = nullptr;
-    return halo_launch(p, st, 0);
+  p.ws = nullptr;
+  switch (r.kernel) {
+    case STEM_S1D:
+      return stem_s1d_launch(p, st);
+    case STEM:
+      return stem_launch(p, st);
+    case HALO:
+      if (stats || part2)
+        STC_REQUIRE(o.stats_chunks == r.chunks, "bf16 conv: stats chunks %d != %d", o.stats_chunks, r.chunks);
+      p.stats = stats;
+      return halo_launch(p, st, r.halo_shape);
+    case BF16_TILE:
+      STC_REQUIRE(!(a.force && a.force[0] == HALO_CFG), "bf16 conv: the halo kernel does not take this shape / view");
+      return bf16_igemm_launch(p, r.bf, o.ws, o.ws_bytes, stats, o.stats_chunks, st);
+    default:
+      return fail(-1, "bf16 conv: route %d is not one of this file's kernels", (int)r.kernel);
   }
-  if (p.vec_out && !force && !stats && bnb && !bnb->g_other.p && stem_s1d_eligible(kind, B, x, Cin, Cout, y)) {
-    p.ws = nullptr;
-    return stem_s1d_launch(p, st);
-  }
-  if (p.vec_out && !force && !stats && (act_n || bnb) && stem_eligible(kind, B, x, Cin, Cout, y, bnb != nullptr)) {
-    p.ws = nullptr;
-    return stem_launch(p, st);
-  }
-  if (!act_n && p.vec_out && halo_plan(force, kind, B, p.GH, p.GW, Cin, Cout) && halo_eligible(kind, B, x, Cin, Cout, y)) {
-    const int need = halo_chunks(kind, B, p.GH, p.GW);
-    if (stats || part2) STC_REQUIRE(stats_chunks == need, "bf16 conv: stats chunks %d != %d", stats_chunks, need);
-    p.stats = stats;
-    p.ws = nullptr;
-    return halo_launch(p, st, force && force[0] == HALO_CFG ? force[1] : 0);
-  }
-  STC_REQUIRE(!(force && force[0] == HALO_CFG), "bf16 conv: the halo kernel does not take this shape / view");
-  return bf16_igemm_launch(p, force, ws, ws_bytes, stats, stats_chunks, st);
-}
-
-// The fused activation backward (stc_conv_bwd_act) runs in the halo kernels' BN-backward epilogue: the layer takes
-// the halo route with 16-byte NHWC bf16 views of one extent.
-bool bf16_conv_bwd_act_ok(int kind, int B, const stc_view& dy, int Cin, int Cout, const stc_view& out, const stc_view& x,
-                          const stc_view* g_other) {
-  if (!bf16_conv_eligible(kind, B, dy, Cin, Cout) || !vec_out_ok(B, out, Cout, 0) || Cout % 8 != 0) return false;
-  const int Hg = kind == STC_CONVT_S2 ? dy.H : out.H, Wg = kind == STC_CONVT_S2 ? dy.W : out.W;
-  if (!halo_plan(nullptr, kind, B, Hg, Wg, Cin, Cout) || !halo_eligible(kind, B, dy, Cin, Cout, out)) return false;
-  auto vec = [&](const stc_view& v) {
-    return v.H == out.H && v.W == out.W && v.cs == 1 && v.co % 8 == 0 && v.ps % 8 == 0 && v.rs % 8 == 0 && v.bs % 8 == 0 &&
-           ((uintptr_t)v.p & 15) == 0 && (long long)B * v.bs < (1ll << 31);
-  };
-  return x.p && vec(x) && (!g_other || !g_other->p || vec(*g_other));
-}
-
-// Partial count of the fused BN-backward sums for these views: the route bf16_conv_fwd takes for a BN-backward
-// call (no statistics, no forced plan) -- the streaming logits-gradient kernel, the streaming Cin = 8 kernel, the
-// halo kernel or the im2col tile -- decides it, so views that one of the streaming / halo kernels does not take
-// (not dense at channel offset 0, a second gradient for the 31 x 31 layer) get the chunk count of the kernel that
-// then runs, not the shape's default.
-int bf16_bnb_chunks(int kind, int B, const stc_view& x, int Cin, int Cout, const stc_view& y, bool g_other) {
-  const int Hg = kind == STC_CONVT_S2 ? x.H : y.H, Wg = kind == STC_CONVT_S2 ? x.W : y.W;
-  if (!g_other && stem_s1d_eligible(kind, B, x, Cin, Cout, y)) return stem_bnb_chunks(kind, B, Hg, Wg, Cin, Cout);
-  if (stem_eligible(kind, B, x, Cin, Cout, y, true)) return stem_bnb_chunks(kind, B, Hg, Wg, Cin, Cout);
-  if (halo_plan(nullptr, kind, B, Hg, Wg, Cin, Cout) && halo_eligible(kind, B, x, Cin, Cout, y))
-    return halo_chunks(kind, B, Hg, Wg);
-  const Geometry g = geometry(kind);
-  const int taps = g.taps_lg_tw == 2 ? 16 : 4;
-  return bf16_problem(B * Hg * Wg, Cout, taps * Cin, g.nphase, nullptr, true).stats_chunks;
-}
-
-// The activation epilogue applies when the layer runs as one LDS-DMA GEMM launch (no split-K) with 16-byte
-// NHWC bf16 views for both outputs.
-bool bf16_conv_act_ok(int kind, int B, const stc_view& x, int Cin, int Cout, const stc_view& y1, const stc_view* y2) {
-  if (!bf16_conv_eligible(kind, B, x, Cin, Cout) || !vec_out_ok(B, y1, Cout, 0) || Cout % 8 != 0) return false;
-  if (y2 && y2->p && (!vec_out_ok(B, *y2, Cout, 0) || y2->H != y1.H || y2->W != y1.W)) return false;
-  const Geometry g = geometry(kind);
-  const int taps = g.taps_lg_tw == 2 ? 16 : 4;
-  const int Hg = kind == STC_CONVT_S2 ? x.H : y1.H, Wg = kind == STC_CONVT_S2 ? x.W : y1.W;
-  const Bf16Problem pr = bf16_problem(B * Hg * Wg, Cout, taps * Cin, g.nphase, nullptr, true);
-  return pr.pl.ksplit == 1;
 }
 
 }  // namespace stc
+

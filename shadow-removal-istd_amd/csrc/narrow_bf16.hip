@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "conv_route.hpp"
 
 namespace stc {
 

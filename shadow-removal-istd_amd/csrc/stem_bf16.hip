@@ -18,6 +18,7 @@
 // rows through a per-wave LDS transpose.  Results equal the im2col tile's bit for bit (same K order, same MFMA).
 #include <algorithm>
 
+#include "conv_route.hpp"
 #include "igemm_bf16.hpp"
 
 namespace stc {

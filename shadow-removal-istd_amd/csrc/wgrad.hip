@@ -19,6 +19,7 @@
 // The pixel dimension is split over blockIdx.z into fp32 slabs that a second kernel
 // sums in a fixed order (bitwise reproducible) while writing torch layout.
 #include "common.hpp"
+#include "conv_route.hpp"
 
 namespace stc {
 
@@ -465,18 +466,6 @@ static WgPlan wg_plan(int P, int R, int Cg) {
   pl.nsplit = cdiv(P, pl.pchunk);
   return pl;
 }
-
-}  // namespace stc
-
-namespace stc {
-bool wgrad_bf16_eligible(int B, const stc_view& D, int R, const stc_view& G, int Cg);
-int64_t wgrad_bf16_workspace(int B, int Hd, int Wd, int R, int Cg, const int32_t* force);
-void wgrad_bf16_plan(int B, int Hd, int Wd, int R, int Cg, const int32_t* force, int32_t* plan_out);
-int wgrad_bf16(int B, int stride, stc_view D, int R, stc_view G, int Cg, int Cg_out, float* dW, void* workspace,
-               int64_t workspace_bytes, hipStream_t st, const int32_t* force);
-}  // namespace stc
-
-namespace stc {
 
 // ---- narrow-R weight gradient of a stride-1 4x4 conv (the PatchGAN logits layer, 512 -> 1 channel:
 // STCGAN/networks.py:183-184).  With RO <= 2 real rows the GEMM form is all im2col traffic (16 taps

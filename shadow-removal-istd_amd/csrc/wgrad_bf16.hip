@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "conv_route.hpp"
 
 #ifndef STC_SETPRIO
 #define STC_SETPRIO 0
@@ -843,8 +844,6 @@ int64_t wgrad_bf16_workspace(int B, int Hd, int Wd, int R, int Cg, const int32_t
   // (no stride here: enough for the stride-2 plan and for the stride-1 one)
   return std::max(wb_ws(wb_plan(B, Hd, Wd, 0, R, Cg, force), R, Cg), wb_ws(wb_plan(B, Hd, Wd, 1, R, Cg, force), R, Cg));
 }
-
-void wgrad_reduce_launch(const float* ws, int nsplit, int R, int Cg, int Cg_out, float* dW, hipStream_t st);
 
 // plan_out = {tile config, BM, BN, pixel splits, slab (1: slabs + reduce kernel)}
 void wgrad_bf16_plan(int B, int Hd, int Wd, int R, int Cg, const int32_t* force, int32_t* plan_out) {

@@ -29,6 +29,7 @@
  *   stc_bn_stats_pack / stc_bn_bwd_sums / stc_bn_bwd_apply_sync  nn.SyncBatchNorm (norm_layer=nn.SyncBatchNorm): the
  *                    same reference lines with the statistics taken over all data-parallel ranks
  *   stc_tanh_bias_bwd Tanh backward + outermost ConvT bias grad (networks.py:112-116)
+ *   stc_head_bwd     the same for every output head (activation = none / tanh / sigmoid / htanh, src/models/opt_layers.py:7-18)
  *   stc_gather_nchw / stc_scatter_nchw              torch.cat input concat (stcgan.py:219-227,269-272) / its backward
  *   stc_loss_fwd / stc_loss_bwd                     DataLoss (L1) and AdversarialLoss (MSE / BCE-with-logits), loss.py:14-26,59-86
  *   stc_conv3_fwd / stc_conv3_pack / stc_conv3_plan  Conv2d 3x3 s1 p1 (+ folded eval BatchNorm, ReLU) of the vgg19_bn
@@ -89,8 +90,14 @@ typedef struct {
  * prologue (applied to every in-bounds input element before the product,
  * zero padding stays zero): v = v*scale[c] + shift[c] (if scale != NULL),
  * then v = v > 0 ? v : v*slope (if pro_act != 0).
- * epilogue: + bias[n] (if bias != NULL), tanh (if epi_tanh).                */
+ * epilogue: + bias[n] (if bias != NULL), then the output head epi_tanh names: an STC_HEAD_* code applied to the
+ * fp32 sum (0 and 1 are what the flag always meant; any other value is an error).  Every non-zero code takes the
+ * route tanh takes: the narrow-N and register-staged kernels.                */
 enum { STC_CONV_S2 = 0, STC_CONV_S1 = 1, STC_CONVT_S2 = 2, STC_CONV_S1_DGRAD = 3 };
+/* The generator's output activation (get_generator(activation=...); src/models/opt_layers.py:7-18), y from the
+ * pre-activation q:  NONE q;  TANH tanhf(q);  SIGMOID 1 / (1 + expf(-q)) in fp32;  HTANH fminf(fmaxf(q, -1), 1)
+ * (nn.Hardtanh(-1, 1)).  DESIGN.md section 8h. */
+enum { STC_HEAD_NONE = 0, STC_HEAD_TANH = 1, STC_HEAD_SIGMOID = 2, STC_HEAD_HTANH = 3 };
 
 int stc_conv_fwd(int dtype, int kind, int B,
                  stc_view x, int Cin,
@@ -448,6 +455,12 @@ int stc_bn_bwd_apply_sync(int dtype, int B, stc_view x, int C,
  * view dq; dbias[c] = sum dq (deterministic).                               */
 int stc_tanh_bias_bwd(int dtype, int B, int C, int H, int W, const float* y, const float* gy,
                       stc_view dq, float* dbias, float* part, int nchunks, void* stream);
+/* The same for any output head act (STC_HEAD_*), from the stored output y alone, the same two kernels and chunk order:
+ *   NONE dq = gy;  TANH as stc_tanh_bias_bwd (identical bits);  SIGMOID omy = 1 - y, dq = gy*(y*omy) (no FMA: what
+ *   torch's fp32 elementwise ops give);  HTANH dq = (-1 < y < 1) ? gy : 0 (torch's hardtanh_backward: y is exactly
+ *   +-1 where q is at or outside the bound).  dbias[c] = sum dq. */
+int stc_head_bwd(int dtype, int act, int B, int C, int H, int W, const float* y, const float* gy,
+                 stc_view dq, float* dbias, float* part, int nchunks, void* stream);
 
 /* ---- layout -------------------------------------------------------------------
  * Gather up to 4 NCHW fp32 sources (channels concatenated, like torch.cat dim=1)

@@ -35,6 +35,10 @@ ap.add_argument("--nn-upconv", type=int, default=0, help="1: generators with Ups
                 "(args.NN_upconv)")
 ap.add_argument("--ab-upconv", action="store_true", help="a second trainer with NN_upconv=True; the two are timed "
                 "alternately, one per repeat (same process)")
+ap.add_argument("--activation", default="tanh", help="the generators' output head: none, sigmoid, tanh, htanh "
+                "(args.activation)")
+ap.add_argument("--ab-activation", default="", help="a second trainer with this output head; the two are timed "
+                "alternately, one per repeat (same process)")
 args = ap.parse_args()
 engine.WGRAD_OVERLAP = args.wgrad_overlap > 0
 if args.wgrad_overlap > 1:
@@ -43,7 +47,8 @@ a = types.SimpleNamespace(devices=["cuda:0"], tasks=["train"], lr_G=5e-5, lr_D=2
                           D_loss_fn="standard", D_loss_type="normal", ngf=64, dtype=args.dtype, load_weights_g1=None,
                           load_weights_g2=None, load_weights_d1=None, load_weights_d2=None,
                           streams=bool(args.streams), fused_objectives=bool(args.fused),
-                          use_dropout=bool(args.use_dropout), droprate=args.droprate, NN_upconv=bool(args.nn_upconv))
+                          use_dropout=bool(args.use_dropout), droprate=args.droprate, NN_upconv=bool(args.nn_upconv),
+                          activation=args.activation)
 torch.manual_seed(1234)
 tr = STCGAN(a)
 drop_trs = None
@@ -52,6 +57,8 @@ if args.ab_dropout:
     drop_trs = [tr, STCGAN(a_d)]
 elif args.ab_upconv:
     drop_trs = [tr, STCGAN(types.SimpleNamespace(**{**vars(a), "NN_upconv": True}))]
+elif args.ab_activation:
+    drop_trs = [tr, STCGAN(types.SimpleNamespace(**{**vars(a), "activation": args.ab_activation}))]
 import stcgan_amd.stcgan as _st  # noqa: E402
 
 
@@ -88,7 +95,9 @@ if args.ab_attr:
 for rep in range(args.repeat):
     if drop_trs:
         tr = drop_trs[rep % 2]
-        drop_label = f"NN_upconv={rep % 2}" if args.ab_upconv else f"use_dropout={rep % 2}"
+        drop_label = (f"NN_upconv={rep % 2}" if args.ab_upconv else
+                      f"activation={(args.activation, args.ab_activation)[rep % 2]}" if args.ab_activation else
+                      f"use_dropout={rep % 2}")
         for _ in range(2):
             tr.train_step(x, m, y)
         torch.cuda.synchronize()

@@ -140,6 +140,30 @@ __device__ __forceinline__ long long vidx(const View& v, int b, int y, int x, in
 __device__ __forceinline__ float act(float v, float slope) { return v > 0.f ? v : v * slope; }
 __device__ __forceinline__ float dact(float n, float slope) { return n > 0.f ? 1.f : slope; }
 
+// The generator's output head (STC_HEAD_*) on the fp32 pre-activation q = acc + bias of a conv
+// epilogue.  code is a kernel argument, the same in every lane: one scalar branch per site, the tanh path the
+// instructions it always was.  Sigmoid is plain fp32 with the library expf (no fast-math intrinsic).
+// (none first: most launches of these kernels carry no head, and then pay the one test they always paid)
+__device__ __forceinline__ float head_act(float q, int code) {
+  if (code == STC_HEAD_NONE) return q;
+  if (code == STC_HEAD_TANH) return tanhf(q);
+  if (code == STC_HEAD_SIGMOID) return 1.f / (1.f + expf(-q));
+  return fminf(fmaxf(q, -1.f), 1.f);
+}
+// dq = gy * head'(q) from the stored output y alone.  Sigmoid in this order has no multiply feeding an add: nothing
+// contracts to an FMA, torch's fp32 elementwise ops give the same bits.  htanh is torch's hardtanh_backward: y is
+// exactly +-1 where q is at or outside the bound.
+__device__ __forceinline__ float head_dq(float gy, float y, int code) {
+  if (code == STC_HEAD_TANH) return gy * (1.f - y * y);
+  if (code == STC_HEAD_SIGMOID) {
+    const float omy = 1.f - y;
+    return gy * (y * omy);
+  }
+  if (code == STC_HEAD_HTANH) return (y > -1.f && y < 1.f) ? gy : 0.f;
+  return gy;
+}
+static inline bool head_code_ok(int code) { return code >= STC_HEAD_NONE && code <= STC_HEAD_HTANH; }
+
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 // blocks of 256 threads for a grid-stride loop over `work` items
 static inline int grid_for(long long work) { return (int)std::max<long long>(1, std::min<long long>((work + 255) / 256, 8192)); }

@@ -35,7 +35,9 @@ struct ConvAsk {  // everything the choice of kernel depends on
   int dtype, kind, B;
   stc_view x, y;
   int Cin, Cout;
-  bool prologue, tanh, out_f32;
+  bool prologue;
+  int tanh;  // the epilogue's output head, an STC_HEAD_* code; the route reads only whether it is non-zero
+  bool out_f32;
   bool stats;               // BatchNorm statistics of the output wanted
   const stc_bnb_fuse* bnb;  // BN-backward sums wanted (bnb_act: the activation backward of a layer without BN instead)
   bool bnb_act;

@@ -151,12 +151,12 @@ __global__ void scatter_kernel(int B, int H, int W, View s, int nsrc, Dst4 d) {
   }
 }
 
-// ------------------------------------------------------------------ tanh + bias backward
-// dq[b,y,x,c] = gy*(1-y^2) for c < C, 0 for C <= c < Cpad (dq view has Cpad channels);
-// part[chunk][c] = sum over the chunk's pixels of dq (c < C)
+// ------------------------------------------------------------------ output head (tanh by default) + bias backward
+// dq[b,y,x,c] = head_dq(gy, y, act) (tanh: gy*(1-y^2)) for c < C, 0 for C <= c < Cpad (dq view has Cpad channels);
+// part[chunk][c] = sum over the chunk's pixels of dq (c < C).  act (STC_HEAD_*) is the same in every lane.
 template <typename T>
 __global__ void tanh_bwd_kernel(int B, int C, int H, int W, const float* y, const float* gy, View dq, int Cpad,
-                                float* part, int nchunks) {
+                                float* part, int nchunks, int act) {
   const long long HW = (long long)H * W, P = HW * B;
   const long long per = (P + nchunks - 1) / nchunks;
   const long long p0 = blockIdx.x * per, p1 = min(P, p0 + per);
@@ -170,8 +170,7 @@ __global__ void tanh_bwd_kernel(int B, int C, int H, int W, const float* y, cons
       float v = 0.f;
       if (c < C) {
         const long long i = ((long long)b * C + c) * HW + hw;
-        const float t = y[i];
-        v = gy[i] * (1.f - t * t);
+        v = head_dq(gy[i], y[i], act);
         acc[c] += v;
       }
       st1<T>(out + (long long)c * dq.cs, v);
@@ -193,7 +192,7 @@ __global__ void tanh_bwd_kernel(int B, int C, int H, int W, const float* y, cons
 // part is summed per thread in pixel order, then over the block in a fixed tree order (deterministic).
 template <typename T>
 __global__ void __launch_bounds__(256) tanh_bwd4_kernel(int B, int C, int HW, int W, const float* y, const float* gy,
-                                                        View dq, int per4, float* part) {
+                                                        View dq, int per4, float* part, int act) {
   const int P = B * HW;
   const int p0 = blockIdx.x * per4, p1 = min(P, p0 + per4);
   float acc[4] = {0, 0, 0, 0};
@@ -209,10 +208,10 @@ __global__ void __launch_bounds__(256) tanh_bwd4_kernel(int B, int C, int HW, in
         const int o = (b * C + c) * HW + hw;
         const float4 t = *reinterpret_cast<const float4*>(y + o);
         const float4 g = *reinterpret_cast<const float4*>(gy + o);
-        v[c][0] = g.x * (1.f - t.x * t.x);
-        v[c][1] = g.y * (1.f - t.y * t.y);
-        v[c][2] = g.z * (1.f - t.z * t.z);
-        v[c][3] = g.w * (1.f - t.w * t.w);
+        v[c][0] = head_dq(g.x, t.x, act);
+        v[c][1] = head_dq(g.y, t.y, act);
+        v[c][2] = head_dq(g.z, t.z, act);
+        v[c][3] = head_dq(g.w, t.w, act);
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[c] += v[c][i];
       }
@@ -413,9 +412,11 @@ extern "C" int stc_scatter_nchw(int dtype, int B, int H, int W, stc_view src, in
   return 0;
 }
 
-extern "C" int stc_tanh_bias_bwd(int dtype, int B, int C, int H, int W, const float* y, const float* gy, stc_view dq,
-                                 float* dbias, float* part, int nchunks, void* stream) {
-  STC_REQUIRE(C >= 1 && C <= 4, "stc_tanh_bias_bwd: C=%d", C);
+extern "C" int stc_head_bwd(int dtype, int act, int B, int C, int H, int W, const float* y, const float* gy,
+                            stc_view dq, float* dbias, float* part, int nchunks, void* stream) {
+  STC_REQUIRE(head_code_ok(act), "stc_head_bwd: act=%d is none of STC_HEAD_* (0..3)", act);
+  STC_REQUIRE(C >= 1 && C <= 4, "stc_head_bwd: C=%d", C);
+  STC_REQUIRE(nchunks >= 1 && part, "stc_head_bwd: nchunks=%d, part required", nchunks);
   hipStream_t st = (hipStream_t)stream;
   const int Cpad = dtype == STC_F32 ? 4 : 8;
   View d = mkview(dq);
@@ -426,19 +427,24 @@ extern "C" int stc_tanh_bias_bwd(int dtype, int B, int C, int H, int W, const fl
   if (quad) {
     const int per4 = (int)((((P + nchunks - 1) / nchunks) + 3) & ~3ll);
     if (dtype == STC_F32)
-      hipLaunchKernelGGL(tanh_bwd4_kernel<float>, dim3(nchunks), dim3(256), 0, st, B, C, H * W, W, y, gy, d, per4, part);
+      hipLaunchKernelGGL(tanh_bwd4_kernel<float>, dim3(nchunks), dim3(256), 0, st, B, C, H * W, W, y, gy, d, per4, part, act);
     else
-      hipLaunchKernelGGL(tanh_bwd4_kernel<bf16>, dim3(nchunks), dim3(256), 0, st, B, C, H * W, W, y, gy, d, per4, part);
+      hipLaunchKernelGGL(tanh_bwd4_kernel<bf16>, dim3(nchunks), dim3(256), 0, st, B, C, H * W, W, y, gy, d, per4, part, act);
   } else if (dtype == STC_F32)
-    hipLaunchKernelGGL(tanh_bwd_kernel<float>, dim3(nchunks), dim3(256), 0, st, B, C, H, W, y, gy, d, Cpad, part, nchunks);
+    hipLaunchKernelGGL(tanh_bwd_kernel<float>, dim3(nchunks), dim3(256), 0, st, B, C, H, W, y, gy, d, Cpad, part, nchunks, act);
   else
-    hipLaunchKernelGGL(tanh_bwd_kernel<bf16>, dim3(nchunks), dim3(256), 0, st, B, C, H, W, y, gy, d, Cpad, part, nchunks);
+    hipLaunchKernelGGL(tanh_bwd_kernel<bf16>, dim3(nchunks), dim3(256), 0, st, B, C, H, W, y, gy, d, Cpad, part, nchunks, act);
   STC_CHECK_LAUNCH();
   if (dbias) {
     hipLaunchKernelGGL(chunk_sum_kernel, dim3(C), dim3(256), 0, st, (const float*)part, nchunks, C, dbias);
     STC_CHECK_LAUNCH();
   }
   return 0;
+}
+
+extern "C" int stc_tanh_bias_bwd(int dtype, int B, int C, int H, int W, const float* y, const float* gy, stc_view dq,
+                                 float* dbias, float* part, int nchunks, void* stream) {
+  return stc_head_bwd(dtype, STC_HEAD_TANH, B, C, H, W, y, gy, dq, dbias, part, nchunks, stream);
 }
 
 extern "C" int stc_loss_parts(int64_t n) { return (int)((n + LOSS_PER_BLOCK - 1) / LOSS_PER_BLOCK); }

@@ -324,7 +324,7 @@ igemm_kernel(const ConvParams p) {
         const long long ro = rowoff[r];
         if (ro < 0) continue;
         float v = acc[i][j][e] + bz;
-        if (p.tanh_) v = tanhf(v);
+        v = head_act(v, p.tanh_);
         if (p.out_f32) reinterpret_cast<float*>(p.c)[ro + coff] = v;
         else st1<T>(reinterpret_cast<T*>(p.c) + ro + coff, v);
       }
@@ -346,7 +346,7 @@ __global__ void splitk_reduce_kernel(const ConvParams p) {
     float v = 0.f;
     for (int s = 0; s < p.ksplit; ++s) v += src[(long long)s * p.M * p.N];
     if (p.bias) v += p.bias[n];
-    if (p.tanh_) v = tanhf(v);
+    v = head_act(v, p.tanh_);
     const int GHW = p.GH * p.GW;
     const int b = m / GHW, rem = m - b * GHW;
     const int y = rem / p.GW, x = rem - y * p.GW;
@@ -427,7 +427,7 @@ __global__ void __launch_bounds__(256) smalln_kernel(const ConvParams p) {
 #pragma unroll
       for (int n = 0; n < NMAX; ++n) if (n == lane) v = acc[n];
       if (p.bias) v += p.bias[lane];
-      if (p.tanh_) v = tanhf(v);
+      v = head_act(v, p.tanh_);
       const int oy = y * p.os + p.oy0[ph], ox = x * p.os + p.ox0[ph];
       const long long off = (long long)b * p.c_bs + (long long)oy * p.c_rs + (long long)ox * p.c_ps +
                             (long long)(p.c_co + lane) * p.c_cs;
@@ -563,7 +563,7 @@ __global__ void narrow_tiled_kernel(const ConvParams p, int tiles_x, int tiles_p
       if (n >= p.N) break;
       float v = acc[q][n];
       if (p.bias) v += p.bias[n];
-      if (p.tanh_) v = tanhf(v);
+      v = head_act(v, p.tanh_);
       const long long off = base + (long long)(p.c_co + n) * p.c_cs;
       if (p.out_f32) reinterpret_cast<float*>(p.c)[off] = v;
       else st1<T>(reinterpret_cast<T*>(p.c) + off, v);
@@ -818,8 +818,9 @@ extern "C" int stc_conv_fwd_ex(int dtype, int kind, int B, stc_view x, int Cin, 
                                int stats_chunks, const int32_t* force_plan, void* workspace, int64_t workspace_bytes,
                                void* stream) {
   STC_REQUIRE(kind >= 0 && kind <= 3, "stc_conv_fwd_ex: bad kind %d", kind);
+  STC_REQUIRE(head_code_ok(epi_tanh), "stc_conv_fwd_ex: epilogue code %d is none of STC_HEAD_* (0..3)", epi_tanh);
   ConvAsk a = conv_ask(dtype, kind, B, x, Cin, Cout, y);
-  a.tanh = epi_tanh != 0; a.out_f32 = out_f32 != 0; a.stats = stats_part != nullptr; a.force = force_plan;
+  a.tanh = epi_tanh; a.out_f32 = out_f32 != 0; a.stats = stats_part != nullptr; a.force = force_plan;
   ConvOps o{};
   o.w = w_packed; o.bias = bias; o.stats = stats_part; o.stats_chunks = stats_chunks;
   o.ws = workspace; o.ws_bytes = workspace_bytes; o.st = (hipStream_t)stream;
@@ -851,8 +852,9 @@ extern "C" int stc_conv_fwd(int dtype, int kind, int B, stc_view x, int Cin,
                             const void* w_packed, int Cout, stc_view y,
                             const float* bias, int epi_tanh, int out_f32,
                             void* workspace, int64_t workspace_bytes, void* stream) {
+  STC_REQUIRE(head_code_ok(epi_tanh), "stc_conv_fwd: epilogue code %d is none of STC_HEAD_* (0..3)", epi_tanh);
   ConvAsk a = conv_ask(dtype, kind, B, x, Cin, Cout, y);
-  a.prologue = pro_scale != nullptr || pro_act != 0; a.tanh = epi_tanh != 0; a.out_f32 = out_f32 != 0;
+  a.prologue = pro_scale != nullptr || pro_act != 0; a.tanh = epi_tanh; a.out_f32 = out_f32 != 0;
   ConvOps o{};
   o.w = w_packed; o.bias = bias;
   o.pro_scale = pro_scale; o.pro_shift = pro_shift; o.pro_act = pro_act; o.pro_slope = pro_slope;

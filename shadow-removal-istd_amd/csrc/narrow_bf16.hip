@@ -232,7 +232,7 @@ __global__ void __launch_bounds__(256) narrow_halo_kernel(const HParams p) {
           int ph = 0, n = np;
           if (GEOM == 0) { ph = np / p.N; n = np - ph * p.N; }
           if (p.bias) v += p.bias[n];
-          if (p.tanh_) v = tanhf(v);
+          v = head_act(v, p.tanh_);
           const int oy = GEOM == 0 ? 2 * gy + (ph >> 1) : gy;
           const int ox = GEOM == 0 ? 2 * gxx + (ph & 1) : gxx;
           store_out(p, (long long)img * p.c_bs + (long long)oy * p.c_rs + (long long)ox * p.c_ps +
@@ -400,7 +400,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) n
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float v = o[rr][cx][e] + bz;
-          if (p.tanh_) v = tanhf(v);
+          v = head_act(v, p.tanh_);
           const int ly = kg * RPW + rr, lx = 16 * cx + 4 * (lane >> 4) + e;
           const int oyl = GEOM == 0 ? 2 * ly + (ph >> 1) : ly, oxl = GEOM == 0 ? 2 * lx + (ph & 1) : lx;
           stg[(oyl * OXL + oxl) * N + n] = v;
@@ -474,8 +474,11 @@ __device__ __forceinline__ void vm_wait_dyn(int n) {
   }
 }
 
-template <int CIN, int NB, int NS>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) narrow_stream_kernel(const HParams p) {
+// HEADS: the sigmoid / htanh output heads compiled in (narrow_stream_heads_kernel).  The default kernel carries the
+// none / tanh test it always had and nothing else: with the two rarer heads behind a branch in the same kernel its
+// code grew by a third and the default path measured 11-12 % slower on both of its shapes.
+template <int CIN, int NB, int NS, bool HEADS>
+__device__ __forceinline__ void narrow_stream_body(const HParams p) {
   constexpr int PXB = CIN * 2;                       // bytes per staged pixel
   constexpr int CH = CIN / 8;                        // 16-byte chunks per pixel
   constexpr int SH = CIN == 64 ? 1 : 0;              // swizzle: chunk ^ ((pixel >> SH) & (CH - 1))
@@ -593,7 +596,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) n
           for (int e = 0; e < 4; ++e) {
             const int gx = x0 + 16 * wave + 4 * cq + e;
             float v = acc[QC][j][e] + bz[j];
-            if (p.tanh_) v = tanhf(v);
+            if constexpr (HEADS) v = head_act(v, p.tanh_);
+            else if (p.tanh_) v = tanhf(v);
             const long long off = (long long)img * p.c_bs + (long long)oy * p.c_rs +
                                   (long long)(2 * gx + (ph[j] & 1)) * p.c_ps + (long long)(p.c_co + nn[j]) * p.c_cs;
             if (on) store_out(p, off, v);
@@ -611,7 +615,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) n
           for (int e = 0; e < 4; ++e) {
             const int px = 2 * (4 * cq + e) + (ph[j] & 1);
             float v = acc[QC][j][e] + bz[j];
-            if (p.tanh_) v = tanhf(v);
+            if constexpr (HEADS) v = head_act(v, p.tanh_);
+            else if (p.tanh_) v = tanhf(v);
             const int o = p.smode == 1 ? ((row * 32 + px) * p.N + nn[j]) * esz : ((nn[j] * 2 + row) * 32 + px) * 4;
             if (p.out_f32) *reinterpret_cast<float*>(stg + o) = v;
             else *reinterpret_cast<unsigned short*>(stg + o) = (unsigned short)(pack_bf16x2(v, 0.f) & 0xffffu);
@@ -643,6 +648,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) n
     step(t + 1, std::integral_constant<int, 1>{});
     step(t + 2, std::integral_constant<int, 2>{});
   }
+}
+
+template <int CIN, int NB, int NS>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) narrow_stream_kernel(const HParams p) {
+  narrow_stream_body<CIN, NB, NS, false>(p);
+}
+template <int CIN, int NB, int NS>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) narrow_stream_heads_kernel(const HParams p) {
+  narrow_stream_body<CIN, NB, NS, true>(p);
 }
 
 // ---- the PatchGAN logits layer (Conv2d k4 s1 p1, CIN -> 1; STCGAN/networks.py:183-184) in two passes: the 16 tap
@@ -705,7 +719,7 @@ __global__ void __launch_bounds__(256) logits_gather_kernel(const HParams p, con
   v += __shfl_xor(v, 2, 64);
   if (ky != 0 || idx >= total) return;
   if (p.bias) v += p.bias[0];
-  if (p.tanh_) v = tanhf(v);
+  v = head_act(v, p.tanh_);
   store_out(p, (long long)b * p.c_bs + (long long)gy * p.c_rs + (long long)gx * p.c_ps + (long long)p.c_co * p.c_cs, v);
 }
 
@@ -722,7 +736,7 @@ __global__ void narrow_reduce_kernel(const HParams p, int B) {
     int ph = 0, n = np;
     if (GEOM == 0) { ph = np / p.N; n = np - ph * p.N; }
     if (p.bias) v += p.bias[n];
-    if (p.tanh_) v = tanhf(v);
+    v = head_act(v, p.tanh_);
     const int img = (int)(m / ((long long)p.GH * p.GW));
     const int rem = (int)(m - (long long)img * p.GH * p.GW);
     const int gy = rem / p.GW, gx = rem - gy * p.GW;
@@ -914,11 +928,15 @@ int bf16_narrow_fwd(int kind, int B, stc_view x, int Cin, const void* w_packed, 
     const int nsl = stream_ns(Cin, force);
     const size_t slds = stream_lds(Cin, nsl);
     main_timer_begin(st);
-#define STC_NS(C_, NB_, S_) \
-  else if (Cin == C_ && nsl == S_) hipLaunchKernelGGL((narrow_stream_kernel<C_, NB_, S_>), sgrid, dim3(256), slds, st, p)
+    const bool heads = p.tanh_ >= STC_HEAD_SIGMOID;
+#define STC_NS(C_, NB_, S_)                                                                                      \
+  else if (Cin == C_ && nsl == S_) {                                                                             \
+    if (heads) hipLaunchKernelGGL((narrow_stream_heads_kernel<C_, NB_, S_>), sgrid, dim3(256), slds, st, p);     \
+    else hipLaunchKernelGGL((narrow_stream_kernel<C_, NB_, S_>), sgrid, dim3(256), slds, st, p);                 \
+  }
     if (false) {}
-    STC_NS(128, 1, 4); STC_NS(128, 1, 3); STC_NS(128, 1, 6); STC_NS(128, 1, 8);
-    STC_NS(64, 2, 6); STC_NS(64, 2, 4);
+    STC_NS(128, 1, 4) STC_NS(128, 1, 3) STC_NS(128, 1, 6) STC_NS(128, 1, 8)
+    STC_NS(64, 2, 6) STC_NS(64, 2, 4)
     else return fail(-1, "narrow bf16: no stream kernel with %d slots", nsl);
 #undef STC_NS
     main_timer_end(st);

@@ -18,6 +18,21 @@ PACK_CONV_FWD, PACK_CONV_DGRAD, PACK_CONV_S1_DGRAD, PACK_CONVT_FWD, PACK_CONVT_D
 PACK_UPCONV_FWD, PACK_UPCONV_DGRAD = 5, 6  # the ConvT operands from an Upsample + Conv2d(3, 1, 1) weight
 LOSS_L1, LOSS_MSE_CONST, LOSS_BCE_CONST = 0, 1, 2
 LOSS_COMBINE_D, LOSS_COMBINE_G = 0, 1
+# STC_HEAD_*: the generator's output activation (conv epilogue code, stc_head_bwd)
+HEAD_NONE, HEAD_TANH, HEAD_SIGMOID, HEAD_HTANH = 0, 1, 2, 3
+HEADS = {"none": HEAD_NONE, "tanh": HEAD_TANH, "sigmoid": HEAD_SIGMOID, "htanh": HEAD_HTANH}
+
+
+def head_code(act):
+    """The STC_HEAD_* code of an output head name ("none" / None, "tanh", "sigmoid", "htanh"); an int is passed
+    through for the library to judge."""
+    if act is None:
+        return HEAD_NONE
+    if isinstance(act, str):
+        if act not in HEADS:
+            raise ValueError(f"stcgan_amd: activation must be 'none', 'sigmoid', 'tanh' or 'htanh', got {act!r}")
+        return HEADS[act]
+    return int(act)
 
 
 class View(ctypes.Structure):
@@ -130,6 +145,7 @@ _SIGS = {
     "stc_bn_bwd_apply_sync": (_i32, [_i32, _i32, View, _i32, _vp, _vp, _vp, _vp, _vp, View, _f32, View, _f32, _vp,
                                      _vp, _i32, _i64, View, _vp]),
     "stc_tanh_bias_bwd": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, View, _vp, _vp, _i32, _vp]),
+    "stc_head_bwd": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, View, _vp, _vp, _i32, _vp]),
     "stc_gather_nchw": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, View, _i32, _vp]),
     "stc_scatter_nchw": (_i32, [_i32, _i32, _i32, _i32, View, _i32, _vp, _vp, _vp]),
     "stc_loss_parts": (_i32, [_i64]),

@@ -21,7 +21,7 @@ channels, S[k] the block-k input resolution (S[1] = S[0]//2, S[k+1] = ceil(S[k]/
          (networks.py:108,143: ReLU of the concat; ReLU(LeakyReLU(v)) = ReLU(v))
          use_dropout, train mode, the levels right above the innermost one: ReLU(BN_u(q_{k+1}) * keep/(1-p)), the
          mask a counter-based function of logical indices (GenPlan.drop, ops.dropout_next)
-  y = tanh(convT_0(cr[0]) + bias), written NCHW fp32.
+  y = head(convT_0(cr[0]) + bias), written NCHW fp32; head = tanh unless get_generator(activation=...) says otherwise.
 
 norm_layer=nn.InstanceNorm2d (GenPlan.inorm / DiscPlan.inorm): the same buffers, with every
 "BN" above an instance norm -- a normed layer is the plain conv, then one instance-norm forward (statistics per sample
@@ -243,6 +243,9 @@ class GenPlan:
         conv.append(outer.model[0])
         up(0, outer.model[3])
         self.out_c = convT[0].out_channels
+        # the output head ("none", "tanh", "sigmoid", "htanh"): read from the module after the outermost up layer, as
+        # dropout's p is read -- it selects the ConvT epilogue and the first backward kernel
+        self.head = _head_of(outer.model, names.get(id(outer), "model"))
         blk = outer.model[1]
         k = 1
         while True:
@@ -282,6 +285,26 @@ class GenPlan:
         self.inorm, self.affine = _norm_kind(list(bnd.values()) + list(bnu.values()))
         self.sync, self.norm_names = _sync_kind(list(bnd.values()) + list(bnu.values()), names)
         self.params = list(net.parameters())
+
+
+def _head_of(seq, name):
+    """The output head of the outermost block's Sequential [downconv, submodule, uprelu, upconv, <activation>]: nothing
+    after the up layer is "none"; nn.Tanh, nn.Sigmoid and nn.Hardtanh(-1, 1) are the other three.  Any other module
+    there (swapped in by hand) raises NotImplementedError naming its path."""
+    nn = torch.nn
+    if len(seq) == 4:
+        return "none"
+    m = seq[4] if len(seq) == 5 else None
+    if type(m) is nn.Tanh:
+        return "tanh"
+    if type(m) is nn.Sigmoid:
+        return "sigmoid"
+    if type(m) is nn.Hardtanh and m.min_val == -1.0 and m.max_val == 1.0:
+        return "htanh"
+    where = f"{name}.model.4" if m is not None else f"{name}.model ({len(seq)} modules)"
+    what = repr(m) if m is not None else "more than one module after the up layer"
+    raise NotImplementedError(f"stcgan_amd: output activation {where}: {what} is not supported -- nothing (none), "
+                              "nn.Tanh, nn.Sigmoid or nn.Hardtanh(-1.0, 1.0)")
 
 
 def _up_layer(m, name):
@@ -578,12 +601,12 @@ def gen_forward(plan, sources, train, dt, cache, save, batch_stats=None):
                                     L.nhwc_view(cr[k - 1], co[k - 1]), 0.0, None, 0.0, drop_of(k), None, save, sync)
         if t is not None:
             tab_u[k] = t
-    # ---- outermost: tanh(convT_0(cr[0]) + bias) -> NCHW fp32
+    # ---- outermost: head(convT_0(cr[0]) + bias) -> NCHW fp32 (plan.head; tanh by default)
     Ho, Wo = 2 * S[1][0], 2 * S[1][1]
     y = torch.empty((B, plan.out_c, Ho, Wo), dtype=torch.float32, device=dev)
     wt0 = ops.packed(cache, plan.convT[0].weight, plan.pack_t_fwd, plan.out_c, 2 * co[0], dt)
     ops.conv(L.CONVT_S2, B, L.nhwc_view(cr[0]), 2 * co[0], wt0, plan.out_c, L.nchw_view(y), dt,
-             bias=plan.convT[0].bias, tanh=True, out_f32=True)
+             bias=plan.convT[0].bias, act=plan.head, out_f32=True)
     saved = None
     if save:
         saved = dict(S=S, xin=xin, rd=rd, ad=ad, cr=cr, rq=rq, tab_d=tab_d, tab_u=tab_u, st_d=st_d, st_u=st_u,
@@ -611,11 +634,15 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
     drops = saved.get("drop") or {}  # {level: dropout level of the forward call} (use_dropout, train mode)
     mode, sync = _norm_mode(plan, not saved["frozen"]), saved["sync"]
     assert (mode == _SYNC) == (sync is not None), "the process group changed between a forward and its backward"
-    # ---- tanh + bias
+    # ---- output head + bias (the default head keeps its own entry: the same call as ever)
     cp = ops.vec(dt)
     Ho, Wo = y.shape[2], y.shape[3]
     dq = _nhwc(B, Ho, Wo, cp, dt, dev)
-    ops.tanh_bias_bwd(y, gy, L.nhwc_view(dq), dt, dbias=W.dest(plan.convT[0].bias) if need_w else None)
+    dbias = W.dest(plan.convT[0].bias) if need_w else None
+    if plan.head == "tanh":
+        ops.tanh_bias_bwd(y, gy, L.nhwc_view(dq), dt, dbias=dbias)
+    else:
+        ops.head_bwd(y, gy, L.nhwc_view(dq), dt, plan.head, dbias=dbias)
     if need_w:
         W.done([plan.convT[0].bias])
     _trace("G", ("dq", 0), dq)

@@ -28,6 +28,10 @@ padding the pair is exactly a ConvTranspose2d whose 4x4 weight is a fixed sum of
 low-resolution input by one pixel), which the zero-filling halo loaders cannot express: out of scope, refused.
 ``conv_t_state_dict()`` exports such a generator as the plain ST-CGAN one.
 
+``activation`` (the ``--activation`` option of the same line, src/models/opt_layers.py:7-18): the generator's output head,
+``"tanh"`` (default), ``"sigmoid"``, ``"htanh"`` (``nn.Hardtanh(-1, 1)``) or ``"none"`` / ``None``; fused into the output
+ConvT's epilogue and the first backward kernel.
+
 Modes are torch's, read from the modules at every call: the network's own ``training`` flag governs the dropout
 levels, its BatchNorm2d children's flags govern batch statistics + running update (train) against running statistics
 with untouched buffers (eval) -- ``net.eval()``, or ``net.train()`` with the norm children in eval (``freeze_norm``).
@@ -104,6 +108,32 @@ def check_norm_layer(norm_layer, use_dropout=False):
         raise NotImplementedError("stcgan_amd: use_dropout=True together with nn.InstanceNorm2d is not supported "
                                   "(the dropout kernels are written against the BatchNorm per-channel tables)")
     return "instance"
+
+
+ACTIVATIONS = ("none", "sigmoid", "tanh", "htanh")
+
+
+def check_activation(v):
+    """A generator output activation as one of ACTIVATIONS (None means "none"; ValueError otherwise)."""
+    if v is None:
+        return "none"
+    if not isinstance(v, str) or v not in ACTIVATIONS:
+        raise ValueError("stcgan_amd: activation must be one of 'none', 'sigmoid', 'tanh', 'htanh' (or None for "
+                         f"'none'), got {v!r}")
+    return v
+
+
+def get_activation(key):
+    """The module of an output activation, as the reference maps it (src/models/opt_layers.py:7-18); None for
+    "none"."""
+    key = check_activation(key)
+    if key == "tanh":
+        return nn.Tanh()
+    if key == "sigmoid":
+        return nn.Sigmoid()
+    if key == "htanh":
+        return nn.Hardtanh(min_val=-1.0, max_val=1.0, inplace=True)
+    return None
 
 
 def check_flag(name, v):
@@ -228,8 +258,14 @@ class UnetGenerator(_HipNet):
     kind = "G"
 
     def __init__(self, in_channels, out_channels, ngf=64, num_downs=8, norm_layer=nn.BatchNorm2d,
-                 use_dropout=False, drop_rate=None, no_conv_t=False):
-        """no_conv_t (the reference's keyword, src/models/opt_layers.py:39-56): each up layer is
+                 use_dropout=False, drop_rate=None, no_conv_t=False, activation="tanh"):
+        """activation (the reference's keyword, src/main.py:295-297, src/models/opt_layers.py:7-18): the module after the
+        outermost up layer -- "tanh" (default) nn.Tanh, "sigmoid" nn.Sigmoid, "htanh" nn.Hardtanh(-1, 1), "none" / None
+        nothing (the outermost Sequential then has 4 modules).  None of them has parameters: every state_dict key is the
+        default generator's and checkpoints load across heads.  The head runs in the output ConvT's epilogue and in the
+        first backward kernel; it is read from that module when the launch plan is made (a module outside this table,
+        swapped in by hand, raises NotImplementedError there).  Composes with every other option.
+        no_conv_t (the reference's keyword, src/models/opt_layers.py:39-56): each up layer is
         nn.Sequential(nn.Upsample(scale_factor=2, mode="nearest"), nn.Conv2d(cin, cout, 3, 1, 1)) at the ConvTranspose2d's
         index, its keys ``...model.N.1.weight`` [cout, cin, 3, 3] (and ``model.3.1.bias`` on the outermost layer).
         padding_mode is "zeros": the reference helper's "reflect" (a replicate halo of the low-resolution input) is
@@ -244,6 +280,7 @@ class UnetGenerator(_HipNet):
         p = check_drop_rate(0.5 if drop_rate is None else drop_rate)
         self._drop_state = None  # device int64 {seed, offset}: a plain attribute, the state_dict keys stay the reference's
         self.no_conv_t = nct = check_flag("no_conv_t", no_conv_t)
+        self.activation = check_activation(activation)
         unet_block = UnetSkipConnectionBlock(ngf * 8, ngf * 8, input_nc=None, submodule=None,
                                              norm_layer=norm_layer, innermost=True, no_conv_t=nct)
         for _ in range(num_downs - 5):
@@ -257,7 +294,8 @@ class UnetGenerator(_HipNet):
         unet_block = UnetSkipConnectionBlock(ngf, ngf * 2, input_nc=None, submodule=unet_block,
                                              norm_layer=norm_layer, no_conv_t=nct)
         self.model = UnetSkipConnectionBlock(out_channels, ngf, input_nc=in_channels, submodule=unet_block,
-                                             outermost=True, norm_layer=norm_layer, no_conv_t=nct)
+                                             outermost=True, norm_layer=norm_layer, no_conv_t=nct,
+                                             activation=self.activation)
 
     def conv_t_state_dict(self):
         """The state_dict of the equivalent plain ST-CGAN generator (ConvTranspose2d up layers): each up layer's
@@ -340,7 +378,7 @@ class UnetSkipConnectionBlock(nn.Module):
     Executed only as part of UnetGenerator (the whole U-Net is one fused HIP schedule)."""
 
     def __init__(self, outer_nc, inner_nc, input_nc=None, submodule=None, outermost=False, innermost=False,
-                 norm_layer=nn.BatchNorm2d, use_dropout=False, drop_rate=0.5, no_conv_t=False):
+                 norm_layer=nn.BatchNorm2d, use_dropout=False, drop_rate=0.5, no_conv_t=False, activation="tanh"):
         super().__init__()
         self.outermost = outermost
         self.innermost = innermost
@@ -361,7 +399,8 @@ class UnetSkipConnectionBlock(nn.Module):
 
         if outermost:
             upconv = up(inner_nc * 2, outer_nc)
-            model = [downconv, submodule, uprelu, upconv, nn.Tanh()]
+            head = get_activation(activation)  # ("none": nothing appended, src/models/unet.py:57-58)
+            model = [downconv, submodule, uprelu, upconv] + ([head] if head is not None else [])
         elif innermost:
             upconv = up(inner_nc, outer_nc, bias=use_bias)
             model = [downrelu, downconv, uprelu, upconv, upnorm]

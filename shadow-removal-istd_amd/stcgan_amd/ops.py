@@ -94,8 +94,12 @@ def plan_of(kind, B, gh, gw, cin, cout, dt):
 
 
 def conv(kind, B, xv, cin, w_packed, cout, yv, dt, pro=None, slope=None, bias=None, tanh=False, out_f32=False,
-         force=None):
-    """Implicit-GEMM conv family (stc_conv_fwd; force: a forced narrow-N tile through stc_conv_fwd_ex, tests)."""
+         force=None, act=None):
+    """Implicit-GEMM conv family (stc_conv_fwd; force: a forced narrow-N tile through stc_conv_fwd_ex, tests).
+    act: the output head of the epilogue (_lib.head_code); tanh=True means act="tanh"."""
+    if act is not None and tanh and L.head_code(act) != L.HEAD_TANH:
+        raise ValueError(f"stcgan_amd: conv(tanh=True) together with act={act!r}")
+    tanh = L.head_code(act) if act is not None else int(bool(tanh))
     dev = w_packed.device
     if kind == L.CONVT_S2:
         gh, gw = xv.H, xv.W
@@ -110,11 +114,11 @@ def conv(kind, B, xv, cin, w_packed, cout, yv, dt, pro=None, slope=None, bias=No
         e0, e1 = _main_events()
     if force is not None:
         assert pro is None and slope is None
-        rc = l.stc_conv_fwd_ex(L.dtype_code(dt), kind, B, xv, cin, ptr(w_packed), cout, yv, ptr(bias), int(tanh),
+        rc = l.stc_conv_fwd_ex(L.dtype_code(dt), kind, B, xv, cin, ptr(w_packed), cout, yv, ptr(bias), tanh,
                                int(out_f32), None, 0, (ctypes.c_int32 * 2)(*force), ptr(ws), nb, stream())
     else:
         rc = l.stc_conv_fwd(L.dtype_code(dt), kind, B, xv, cin, sc, sh, 0 if slope is None else 1,
-                            0.0 if slope is None else float(slope), ptr(w_packed), cout, yv, ptr(bias), int(tanh),
+                            0.0 if slope is None else float(slope), ptr(w_packed), cout, yv, ptr(bias), tanh,
                             int(out_f32), ptr(ws), nb, stream())
     if timer is not None:
         _disarm()
@@ -1023,6 +1027,18 @@ def tanh_bias_bwd(y, gy, dqv, dt, dbias=None):
     dbias = _out1(dbias, C, y.device)
     check(lib().stc_tanh_bias_bwd(L.dtype_code(dt), B, C, H, W, ptr(y), ptr(gy), dqv, ptr(dbias), ptr(part), nch,
                                   stream()), "stc_tanh_bias_bwd")
+    return dbias
+
+
+def head_bwd(y, gy, dqv, dt, act, dbias=None):
+    """tanh_bias_bwd for any output head ``act`` (_lib.head_code): dq = gy * act'(q) from the stored output y into the NHWC
+    view dqv (padded channels zero); returns dbias [C] (into ``dbias`` when given).  stc_head_bwd."""
+    B, C, H, W = y.shape
+    nch = stats_chunks(B, H, W)
+    part = torch.empty((nch, C), dtype=torch.float32, device=y.device)
+    dbias = _out1(dbias, C, y.device)
+    check(lib().stc_head_bwd(L.dtype_code(dt), L.head_code(act), B, C, H, W, ptr(y), ptr(gy), dqv, ptr(dbias),
+                             ptr(part), nch, stream()), "stc_head_bwd")
     return dbias
 
 

@@ -163,6 +163,13 @@ def check_norm(v):
     return _NORM_LAYERS[v]
 
 
+def check_activation(v):
+    """args.activation: "none", "sigmoid", "tanh" or "htanh" (ValueError otherwise; None is not an args value)."""
+    if not isinstance(v, str):
+        raise ValueError("stcgan_amd: args.activation must be 'none', 'sigmoid', 'tanh' or 'htanh', got " + repr(v))
+    return networks.check_activation(v)
+
+
 def check_nn_upconv(v):
     """args.NN_upconv as a bool (True / False / 0 / 1; ValueError otherwise)."""
     return networks.check_flag("args.NN_upconv", v)
@@ -205,6 +212,12 @@ class STCGAN(object):
         # nearest-neighbour upsampling + 3x3 conv instead of ConvTranspose2d (networks.UnetGenerator, no_conv_t)
         self.NN_upconv = check_nn_upconv(getattr(args, "NN_upconv", False))
         up = dict(no_conv_t=True) if self.NN_upconv else {}
+        # args.activation ("tanh"; the --activation option of the reference's src/ line): the output head of both
+        # generators, "none", "sigmoid", "tanh" or "htanh" (networks.UnetGenerator, activation).  infer()'s output stage
+        # and VisualLoss keep mapping y*0.5+0.5 whatever the head, as the reference keeps its Normalize inverse: with
+        # "sigmoid" or "none" the caller's targets decide what that range means.
+        self.activation = check_activation(getattr(args, "activation", "tanh"))
+        up["activation"] = self.activation
         self.G1 = networks.get_generator(in_channels=3, out_channels=1, ngf=ngf, **nl, **drop, **up)
         self.G2 = networks.get_generator(in_channels=3 + 1, out_channels=3, ngf=ngf, **nl, **drop, **up)
         self.D1 = networks.get_discriminator(in_channels=3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False, **nl)

@@ -14,6 +14,9 @@
  *   stc_conv_fwd_ex  the same forward with the BatchNorm batch statistics of its output fused in
  *                    (Conv/ConvT -> BatchNorm2d pairs, networks.py:104-109,112-121,167-170,176-179)
  *   stc_conv_bwd_bn  input-gradient conv with the consumer BatchNorm-backward reduction fused in
+ *   stc_conv_pad_fwd / stc_conv_pad_dgrad / stc_conv_pad_wgrad  Conv2d 4x4 s2/s1 p1 with a padding mode: forward,
+ *                    input gradient and weight gradient of nn.Conv2d(..., padding_mode="reflect")
+ *                    (src/models/mnet.py, patchgan.py, unet.py and get_upsample build their convs so); DESIGN.md 8i
  *   stc_pack_weight / stc_pack_weights  torch weight layout -> GEMM operand layout (one / many tensors)
  *   stc_upconv_expand / stc_upconv_wgrad_collapse  nn.Upsample(2, nearest) + Conv2d 3x3 s1 p1 up layers (no_conv_t /
  *                    --NN-upconv, src/models/opt_layers.py:39-56) as the equivalent ConvTranspose2d: the weight map
@@ -241,6 +244,57 @@ int stc_conv_wgrad_ex(int dtype, int B, int stride,
                       float* dW, const int32_t* force_plan, void* workspace, int64_t workspace_bytes, void* stream);
 int stc_conv_wgrad_query(int dtype, int B, int Hd, int Wd, int R, int Cg, const int32_t* force_plan,
                          int64_t* workspace_bytes, int32_t* plan_out);
+/* ---- Conv2d k4 p1 with a padding mode (nn.Conv2d(..., padding_mode=...)) --------------------------------
+ * pad_mode: STC_PAD_ZEROS, the halo every entry point above assumes, or STC_PAD_REFLECT: the one-wide halo mirrors
+ * the plane about its border pixel, index map R(j) = -j for j < 0 and 2(H-1) - j for j >= H (only R(-1) = 1 and
+ * R(H) = H - 2 occur), as F.pad(x, (1, 1, 1, 1), mode="reflect") followed by a padding-free conv.
+ * kind is the Conv2d kind of the layer in all three calls (STC_CONV_S2 or STC_CONV_S1).  Packed weights are the
+ * existing pack modes (STC_PACK_CONV_FWD for the forward, STC_PACK_CONV_DGRAD / STC_PACK_CONV_S1_DGRAD for the
+ * input gradient); the weight gradient is written in torch layout.
+ *
+ * With STC_PAD_ZEROS each call is the existing one, bit for bit: stc_conv_pad_fwd = stc_conv_fwd_ex,
+ * stc_conv_pad_dgrad = stc_conv_fwd_ex of kind STC_CONVT_S2 / STC_CONV_S1_DGRAD, stc_conv_pad_wgrad =
+ * stc_conv_wgrad_ex without prologues; the queries likewise.
+ *
+ * With STC_PAD_REFLECT:
+ *   forward          y[oy,ox] = sum x[R(s oy + kh - 1), R(s ox + kw - 1)] w[kh,kw]: the register-staged tile kernel
+ *                    or the wave-per-pixel narrow-N kernel with the gather index remapped.  Statistics asked for
+ *                    (stats_part) come from stc_chan_stats over the stored output: no reflect call takes a fused
+ *                    statistics, BN-backward or activation epilogue.
+ *   weight gradient  the same remap on the G operand (the conv's input), register-staged kernel.
+ *   input gradient   the adjoint is not a remap: pixel row 1 also receives what a virtual row -1 would, row H - 2
+ *                    what row H would (columns alike, corners up to three extra terms).  The padding-free transposed
+ *                    conv is run over the extended grid -1 .. H, -1 .. W into an fp32 frame in the workspace (the
+ *                    existing kernels, split-K included), then one launch folds frame (a, b) into (R(a), R(b)):
+ *                    a fixed-order fp32 sum of up to 9 frame values per element, rounded once on store.  No atomics.
+ * Every argument is judged before anything is launched: dtype, kind a Conv2d kind, pad_mode one of the two, operand
+ * pointers non-null, force_plan NULL under reflect (the reflect kernels have one automatic plan; with STC_PAD_ZEROS it
+ * means what it means to the existing entry point), and under reflect the conv's input extent >= 2 in both dimensions (torch: "Padding size should be less
+ * than the corresponding input dimension").  Failures return non-zero with the reason in stc_last_error().
+ *
+ * The queries take the conv's INPUT extent H x W (the extent of x / dx) and answer for dense NHWC views:
+ * workspace bytes (split-K slabs, plus the frame for the input gradient), statistics chunks (forward) and
+ * plan_out[5] = {BM, BN, ksplit, narrow_n, tile config} (forward, input gradient: of the frame conv) or
+ * {-1, BM, BN, pixel splits, slab} (weight gradient), as stc_conv_fwd_query / stc_conv_wgrad_query report them.
+ * stc_conv_pad_wgrad_query takes the output grid Hd x Wd as stc_conv_wgrad_query does. */
+enum { STC_PAD_ZEROS = 0, STC_PAD_REFLECT = 1 };
+int stc_conv_pad_fwd(int dtype, int kind, int pad_mode, int B, stc_view x, int Cin, const void* w_packed, int Cout,
+                     stc_view y, const float* bias, int epi_tanh, int out_f32, float* stats_part, int stats_chunks,
+                     const int32_t* force_plan, void* workspace, int64_t workspace_bytes, void* stream);
+int stc_conv_pad_fwd_query(int dtype, int kind, int pad_mode, int B, int H, int W, int Cin, int Cout, int out_f32,
+                           const int32_t* force_plan, int64_t* workspace_bytes, int32_t* stats_chunks,
+                           int32_t* plan_out);
+/* dy: the gradient of the conv's output (Cout channels), dx: the gradient of its input (Cin channels, extent H x W) */
+int stc_conv_pad_dgrad(int dtype, int kind, int pad_mode, int B, stc_view dy, int Cout, const void* w_packed, int Cin,
+                       stc_view dx, int out_f32, void* workspace, int64_t workspace_bytes, void* stream);
+int stc_conv_pad_dgrad_query(int dtype, int kind, int pad_mode, int B, int H, int W, int Cout, int Cin, int out_f32,
+                             int64_t* workspace_bytes, int32_t* plan_out);
+/* dW[R][Cg_out][4][4] from dy (R channels, the output grid) and x (Cg channels, the conv's input) */
+int stc_conv_pad_wgrad(int dtype, int kind, int pad_mode, int B, stc_view dy, int R, stc_view x, int Cg, int Cg_out,
+                       float* dW, const int32_t* force_plan, void* workspace, int64_t workspace_bytes, void* stream);
+int stc_conv_pad_wgrad_query(int dtype, int kind, int pad_mode, int B, int Hd, int Wd, int R, int Cg,
+                             const int32_t* force_plan, int64_t* workspace_bytes, int32_t* plan_out);
+
 /* Narrow-R stride-1 weight gradient (the PatchGAN logits layer, 512 -> 1: STCGAN/networks.py:183-184):
  * as stc_conv_wgrad for stride 1 when only the first R_out (1..2) of the R channels of D are nonzero
  * (channel padding); rows R_out..R-1 of dW are written as zeros.  D: [B][G.H-1][G.W-1][>=R],

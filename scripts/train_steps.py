@@ -39,6 +39,8 @@ ap.add_argument("--activation", default="tanh", help="the generators' output hea
                 "(args.activation)")
 ap.add_argument("--ab-activation", default="", help="a second trainer with this output head; the two are timed "
                 "alternately, one per repeat (same process)")
+ap.add_argument("--padding-mode", default="zeros", help="the padding mode of every 4x4 conv of all four networks: "
+                "zeros, reflect (args.padding_mode)")
 args = ap.parse_args()
 engine.WGRAD_OVERLAP = args.wgrad_overlap > 0
 if args.wgrad_overlap > 1:
@@ -48,7 +50,7 @@ a = types.SimpleNamespace(devices=["cuda:0"], tasks=["train"], lr_G=5e-5, lr_D=2
                           load_weights_g2=None, load_weights_d1=None, load_weights_d2=None,
                           streams=bool(args.streams), fused_objectives=bool(args.fused),
                           use_dropout=bool(args.use_dropout), droprate=args.droprate, NN_upconv=bool(args.nn_upconv),
-                          activation=args.activation)
+                          activation=args.activation, padding_mode=args.padding_mode)
 torch.manual_seed(1234)
 tr = STCGAN(a)
 drop_trs = None
@@ -87,7 +89,8 @@ torch.cuda.synchronize()
 ab = [int(v) for v in args.ab.split(",")] if args.ab else None
 plans = json.loads(args.ab_plans) if args.ab_plans else None
 res = {}
-drop_label = f"use_dropout={args.use_dropout}" + (f", NN_upconv={args.nn_upconv}" if args.nn_upconv else "")
+drop_label = (f"use_dropout={args.use_dropout}" + (f", NN_upconv={args.nn_upconv}" if args.nn_upconv else "")
+              + (f", padding_mode={args.padding_mode}" if args.padding_mode != "zeros" else ""))
 attr = None
 if args.ab_attr:
     an, av = args.ab_attr.split("=")

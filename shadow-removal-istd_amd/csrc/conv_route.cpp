@@ -15,6 +15,39 @@ ConvRoute conv_route(const ConvAsk& a) {
   const int M = B * GH * GW, K = taps * Cin;
   r.GH = GH;
   r.GW = GW;
+  if (a.pad == STC_PAD_REFLECT) {
+    // Reflect padding: only the two gather kernels of igemm.hip implement it -- the register-staged tile and the
+    // wave-per-pixel narrow-N kernel -- and nothing is fused: statistics, BN-backward sums and activations come
+    // from passes over the stored output (for the input gradient they would be formed before the fold).
+    if (a.prologue || a.bnb || a.act_n) return r;  // CONV_NONE: no such form
+    const bool dgrad = convt || kind == STC_CONV_S1_DGRAD;
+    int gh = GH, gw = GW;
+    if (dgrad) {  // the frame conv's grid: every index -1 .. H of the input gradient's extent (y), per phase for s2
+      gh = convt ? (a.y.H + 3) / 2 : a.y.H + 2;
+      gw = convt ? (a.y.W + 3) / 2 : a.y.W + 2;
+      r.FH = convt ? 2 * gh : gh;
+      r.FW = convt ? 2 * gw : gw;
+      r.frame_bytes = (int64_t)B * r.FH * r.FW * Cout * 4;
+    }
+    r.GH = gh;
+    r.GW = gw;
+    const int m = B * gh * gw;
+    const long long P = (long long)m * (g.nphase == 4 ? 4 : 1);
+    r.chunks = stc_chan_stats_chunks(1, 1, (int)std::min<long long>(P, 1 << 30));
+    r.plan[2] = 1;
+    r.plan[4] = -1;
+    if (use_smalln(a.dtype, Cout, K)) {
+      r.kernel = SMALLN;
+      r.plan[0] = 1; r.plan[1] = Cout; r.plan[3] = 1;
+      r.ws_bytes = r.frame_bytes;
+      return r;
+    }
+    r.kernel = FP_TILE;
+    r.fp = fp_tile_plan(a.dtype, m, Cout, K, g.nphase);
+    r.ws_bytes = r.frame_bytes + (r.fp.ksplit <= 1 ? 0 : (int64_t)g.nphase * r.fp.ksplit * (int64_t)m * Cout * 4);
+    r.plan[0] = r.fp.BM; r.plan[1] = r.fp.BN; r.plan[2] = r.fp.ksplit;
+    return r;
+  }
   const bool plain = a.dtype == STC_BF16 && !a.prologue;  // what the bf16-only kernels take
   auto smalln_at = [&](int k) { return use_smalln(a.dtype, Cout, k); };
   auto vec_out = [&](const stc_view& v, bool f32) { return vec_out_ok(B, v, Cout, f32) && Cout % 8 == 0; };

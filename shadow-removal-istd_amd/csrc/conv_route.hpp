@@ -44,6 +44,10 @@ struct ConvAsk {  // everything the choice of kernel depends on
   int act_n;  // activation epilogue: 1 or 2 activated copies (the second into *act2)
   const stc_view* act2;
   const int32_t* force;  // force_plan
+  // STC_PAD_ZEROS, or STC_PAD_REFLECT.  A reflect ask of a Conv2d kind is the layer's forward;
+  // one of kind STC_CONVT_S2 / STC_CONV_S1_DGRAD is the layer's input gradient, y the gradient of its input: the
+  // padding-free transposed conv over the extended grid into an fp32 frame, then the fold
+  int pad;
 };
 
 enum ConvKernel { CONV_NONE, FP_TILE, SMALLN, NARROW_TILED, BF16_NARROW, STEM, STEM_S1D, HALO, BF16_TILE };
@@ -61,6 +65,10 @@ struct ConvRoute {
   const int32_t* narrow_force;  // BF16_NARROW: the forced tile, or NULL
   FpPlan fp;                    // FP_TILE
   Bf16Problem bf;               // BF16_TILE
+  // a reflect input gradient: the fp32 frame [B][FH][FW][Cout] at the head of the workspace (frame_bytes of
+  // ws_bytes; 0 for every other ask), the split-K slabs behind it
+  int FH, FW;
+  int64_t frame_bytes;
 };
 
 ConvRoute conv_route(const ConvAsk& a);

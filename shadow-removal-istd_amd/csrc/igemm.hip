@@ -92,245 +92,29 @@ __device__ __forceinline__ uint4 prologue16(uint4 v, const float* sc, const floa
   return r;
 }
 
+// Reflect padding (STC_PAD_REFLECT): the one-wide halo of a Conv2d k4 p1 reads the plane
+// mirrored about its border pixel, R(-1) = 1 and R(H) = H - 2 -- the only two out-of-range indices the taps reach.
+// Any other index is returned as it came (rows past M stay out of bounds).
+__device__ __forceinline__ int reflect1(int j, int H) { return j == -1 ? 1 : (j == H ? H - 2 : j); }
+
 template <typename T, int BM, int BN, int WM, int WN, bool PRO>
 __global__ void __launch_bounds__(256, 2)
 igemm_kernel(const ConvParams p) {
-  constexpr int VEC = 16 / sizeof(T);
-  constexpr int BK = 128 / sizeof(T);
-  constexpr int AIT = BM / 32;  // 16-byte chunks per thread for A (8 chunks per row)
-  constexpr int BIT = BN / 32;
-  constexpr int WTM = BM / WM, WTN = BN / WN;
-  constexpr int FM = WTM / 32, FN = WTN / 32;
-  constexpr int STAGE = (BM + BN) * LDS_ROW;
-  static_assert(WM * WN == 4, "4 waves");
-  static_assert(FM >= 1 && FN >= 1, "wave tile >= 32x32");
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  long long* rowoff = reinterpret_cast<long long*>(smem + 2 * STAGE);
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN;
-
-  // XCD-aware bijective remap of the flat tile id: consecutive tiles (sharing A rows)
-  // land on the same XCD's L2.
-  const int nwg = p.mtiles * p.ntiles;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int mt = bid / p.ntiles, nt = bid % p.ntiles;
-  const int m0 = mt * BM, n0 = nt * BN;
-  const int z = blockIdx.z;
-  const int ph = z / p.ksplit, split = z % p.ksplit;
-  const int kbeg = split * p.kchunk;
-  const int kend = min(p.K, kbeg + p.kchunk);
-  const int nsteps = (kend - kbeg + BK - 1) / BK;  // a partial last step is zero-filled past kend
-  const int GHW = p.GH * p.GW;
-  const int offy = p.offy[ph], offx = p.offx[ph];
-  const int tw_mask = (1 << p.lg_tw) - 1;
-
-  // ---- per-thread A row info
-  const int ca = tid & 7;
-  long long abase[AIT];
-  int ayy[AIT], axx[AIT];
-#pragma unroll
-  for (int i = 0; i < AIT; ++i) {
-    const int m = m0 + (tid >> 3) + 32 * i;
-    if (m < p.M) {
-      const int b = m / GHW, rem = m - b * GHW;
-      const int y = rem / p.GW, x = rem - y * p.GW;
-      abase[i] = (long long)b * p.a_bs + p.a_co;
-      ayy[i] = y * p.in_stride + offy;
-      axx[i] = x * p.in_stride + offx;
-    } else {
-      abase[i] = 0;
-      ayy[i] = -100000;  // always out of bounds
-      axx[i] = -100000;
-    }
-  }
-  // ---- per-thread B row info
-  const T* bptr[BIT];
-  bool bval[BIT];
-#pragma unroll
-  for (int j = 0; j < BIT; ++j) {
-    const int n = n0 + (tid >> 3) + 32 * j;
-    bval[j] = n < p.N;
-    bptr[j] = reinterpret_cast<const T*>(p.b) + p.b_phase_stride * ph + (long long)(bval[j] ? n : 0) * p.K + ca * VEC;
-  }
-  // ---- output row offsets (direct epilogue)
-  if (!p.ws) {
-    for (int r = tid; r < BM; r += 256) {
-      const int m = m0 + r;
-      long long off = -1;
-      if (m < p.M) {
-        const int b = m / GHW, rem = m - b * GHW;
-        const int y = rem / p.GW, x = rem - y * p.GW;
-        const int oy = y * p.os + p.oy0[ph], ox = x * p.os + p.ox0[ph];
-        off = (long long)b * p.c_bs + (long long)oy * p.c_rs + (long long)ox * p.c_ps;
-      }
-      rowoff[r] = off;
-    }
-  }
-
-  // Two register staging sets (ping-pong): the global loads of K-step s+2 are issued at
-  // step s and written to LDS at the end of step s+1, so two steps of MFMA work cover
-  // their latency (a bf16 K-step is only 16 MFMAs per wave).
-  struct Regs {
-    uint4 ra[AIT], rb[BIT];
-    unsigned amask;  // which A chunks were in bounds (prologue must not touch padding)
-    int aci;         // channel of this thread's chunk in the staged K-step
-  };
-  Regs r0, r1;
-  const T* abase_ptr = reinterpret_cast<const T*>(p.a);
-  constexpr bool has_pro = PRO;  // the engine materialises activations: PRO=false on its hot path
-
-  auto load_regs = [&](Regs& R, int k0) {
-    const int k = k0 + ca * VEC;
-    const int t = k / p.cin, ci = k - t * p.cin;
-    const int dy = p.stepy * (t >> p.lg_tw), dx = p.stepx * (t & tw_mask);
-    R.aci = ci;
-    R.amask = 0;
-    const bool kin = k < kend;
-#pragma unroll
-    for (int i = 0; i < AIT; ++i) {
-      const int iy = ayy[i] + dy, ix = axx[i] + dx;
-      if (kin && (unsigned)iy < (unsigned)p.IH && (unsigned)ix < (unsigned)p.IW) {
-        const T* src = abase_ptr + abase[i] + (long long)iy * p.a_rs + (long long)ix * p.a_ps + ci;
-        R.ra[i] = *reinterpret_cast<const uint4*>(src);
-        R.amask |= 1u << i;
-      } else {
-        R.ra[i] = make_uint4(0, 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < BIT; ++j) {
-      R.rb[j] = (bval[j] && kin) ? *reinterpret_cast<const uint4*>(bptr[j] + k0) : make_uint4(0, 0, 0, 0);
-    }
-  };
-  auto store_lds = [&](Regs& R, int stage) {
-    char* sA = smem + stage * STAGE;
-    char* sB = sA + BM * LDS_ROW;
-#pragma unroll
-    for (int i = 0; i < AIT; ++i) {
-      uint4 v = R.ra[i];
-      if (has_pro && (R.amask >> i & 1u)) v = prologue16<T>(v, p.sc, p.sh, R.aci, p.pro_act, p.slope);
-      *reinterpret_cast<uint4*>(sA + ((tid >> 3) + 32 * i) * LDS_ROW + ca * 16) = v;
-    }
-#pragma unroll
-    for (int j = 0; j < BIT; ++j)
-      *reinterpret_cast<uint4*>(sB + ((tid >> 3) + 32 * j) * LDS_ROW + ca * 16) = R.rb[j];
-  };
-
-  floatx16 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  const int lrow = lane & 31, lhalf = lane >> 5;
-  auto compute = [&](int cur) {
-    const char* sA = smem + cur * STAGE;
-    const char* sB = sA + BM * LDS_ROW;
-#pragma unroll
-    for (int kc = 0; kc < 4; ++kc) {
-      const int coff = (2 * kc + lhalf) * 16;
-      uint4 fa[FM], fb[FN];
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-        fa[i] = *reinterpret_cast<const uint4*>(sA + (wm * WTM + 32 * i + lrow) * LDS_ROW + coff);
-#pragma unroll
-      for (int j = 0; j < FN; ++j)
-        fb[j] = *reinterpret_cast<const uint4*>(sB + (wn * WTN + 32 * j + lrow) * LDS_ROW + coff);
-      if constexpr (sizeof(T) == 4) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-          for (int i = 0; i < FM; ++i) {
-            const float av = __uint_as_float(e == 0 ? fa[i].x : e == 1 ? fa[i].y : e == 2 ? fa[i].z : fa[i].w);
-#pragma unroll
-            for (int j = 0; j < FN; ++j) {
-              const float bv = __uint_as_float(e == 0 ? fb[j].x : e == 1 ? fb[j].y : e == 2 ? fb[j].z : fb[j].w);
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-            }
-          }
-        }
-      } else {
-        typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-#pragma unroll
-        for (int i = 0; i < FM; ++i) {
-          const bf16x8 av = __builtin_bit_cast(bf16x8, fa[i]);
-#pragma unroll
-          for (int j = 0; j < FN; ++j) {
-            const bf16x8 bv = __builtin_bit_cast(bf16x8, fb[j]);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[i][j], 0, 0, 0);
-          }
-        }
-      }
-    }
-  };
-
-  if (nsteps > 0) {
-    load_regs(r0, kbeg);
-    store_lds(r0, 0);
-  }
-  if (nsteps > 1) load_regs(r1, kbeg + BK);
-  __syncthreads();
-  // step s: set (s&1) held step s (already in LDS stage s&1); set ((s+1)&1) holds step s+1
-  for (int s = 0; s < nsteps; s += 2) {
-    if (s + 2 < nsteps) load_regs(r0, kbeg + (s + 2) * BK);
-    compute(0);
-    if (s + 1 < nsteps) store_lds(r1, 1);
-    __syncthreads();
-    if (s + 1 >= nsteps) break;
-    if (s + 3 < nsteps) load_regs(r1, kbeg + (s + 3) * BK);
-    compute(1);
-    if (s + 2 < nsteps) store_lds(r0, 0);
-    __syncthreads();
-  }
-
-  // ---- epilogue
-  if (p.ws) {
-    float* slab = p.ws + (long long)z * p.M * p.N;
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const int n = n0 + wn * WTN + 32 * j + lrow;
-        if (n >= p.N) continue;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int m = m0 + wm * WTM + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * lhalf;
-          if (m < p.M) slab[(long long)m * p.N + n] = acc[i][j][e];
-        }
-      }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < FN; ++j) {
-    const int n = n0 + wn * WTN + 32 * j + lrow;
-    if (n >= p.N) continue;
-    const float bz = p.bias ? p.bias[n] : 0.f;
-    const long long coff = (long long)(p.c_co + n) * p.c_cs;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int r = wm * WTM + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * lhalf;
-        const long long ro = rowoff[r];
-        if (ro < 0) continue;
-        float v = acc[i][j][e] + bz;
-        v = head_act(v, p.tanh_);
-        if (p.out_f32) reinterpret_cast<float*>(p.c)[ro + coff] = v;
-        else st1<T>(reinterpret_cast<T*>(p.c) + ro + coff, v);
-      }
-    }
-  }
+#define STC_HALO_REMAP(iy, ix, IH, IW)
+#include "igemm_tile.inc"
+#undef STC_HALO_REMAP
 }
+
+// the same tile with the reflected halo (the engine materialises activations: no prologue form)
+template <typename T, int BM, int BN, int WM, int WN>
+__global__ void __launch_bounds__(256, 2)
+igemm_reflect_kernel(const ConvParams p) {
+  constexpr bool PRO = false;
+#define STC_HALO_REMAP(iy, ix, IH, IW) iy = reflect1(iy, IH); ix = reflect1(ix, IW);
+#include "igemm_tile.inc"
+#undef STC_HALO_REMAP
+}
+
 
 // Split-K / raw-slab reduction with the epilogue: out[m, n] = epi(sum_s ws[ph][s][m][n])
 template <typename T>
@@ -366,76 +150,18 @@ __global__ void splitk_reduce_kernel(const ConvParams p) {
 // in LDS, and a wave shuffle reduces the N partial dots.
 template <typename T>
 __global__ void __launch_bounds__(256) smalln_kernel(const ConvParams p) {
-  constexpr int VEC = 16 / sizeof(T);
-  constexpr int NMAX = 8;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  T* wl = reinterpret_cast<T*>(smem);  // [N][K] of this phase
-  const int ph = blockIdx.y;
-  const T* wsrc = reinterpret_cast<const T*>(p.b) + p.b_phase_stride * ph;
-  const int NK = p.N * p.K;
-  for (int i = threadIdx.x * VEC; i < NK; i += 256 * VEC)
-    *reinterpret_cast<uint4*>(wl + i) = *reinterpret_cast<const uint4*>(wsrc + i);
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nchunks = p.K / VEC;
-  const int GHW = p.GH * p.GW;
-  const int tw_mask = (1 << p.lg_tw) - 1;
-  const int offy = p.offy[ph], offx = p.offx[ph];
-  const T* A = reinterpret_cast<const T*>(p.a);
-  for (int m = blockIdx.x * 4 + wave; m < p.M; m += gridDim.x * 4) {
-    const int b = m / GHW, rem = m - b * GHW;
-    const int y = rem / p.GW, x = rem - y * p.GW;
-    const long long abase = (long long)b * p.a_bs + p.a_co;
-    float acc[NMAX];
-#pragma unroll
-    for (int n = 0; n < NMAX; ++n) acc[n] = 0.f;
-    for (int c = lane; c < nchunks; c += 64) {
-      const int k = c * VEC;
-      const int t = k / p.cin, ci = k - t * p.cin;
-      const int iy = y * p.in_stride + offy + p.stepy * (t >> p.lg_tw);
-      const int ix = x * p.in_stride + offx + p.stepx * (t & tw_mask);
-      if ((unsigned)iy >= (unsigned)p.IH || (unsigned)ix >= (unsigned)p.IW) continue;
-      uint4 v = *reinterpret_cast<const uint4*>(A + abase + (long long)iy * p.a_rs + (long long)ix * p.a_ps + ci);
-      if (p.sc || p.pro_act) v = prologue16<T>(v, p.sc, p.sh, ci, p.pro_act, p.slope);
-      float av[VEC];
-      if constexpr (sizeof(T) == 4) {
-        av[0] = __uint_as_float(v.x); av[1] = __uint_as_float(v.y);
-        av[2] = __uint_as_float(v.z); av[3] = __uint_as_float(v.w);
-      } else {
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { av[2 * q] = __uint_as_float(w[q] << 16); av[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u); }
-      }
-#pragma unroll
-      for (int n = 0; n < NMAX; ++n) {
-        if (n >= p.N) break;
-        const T* wr = wl + n * p.K + k;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) acc[n] = fmaf(av[e], ld1<T>(wr + e), acc[n]);
-      }
-    }
-#pragma unroll
-    for (int n = 0; n < NMAX; ++n) {
-      if (n >= p.N) break;
-      float s = acc[n];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-      acc[n] = s;
-    }
-    if (lane < p.N) {
-      float v = 0.f;
-#pragma unroll
-      for (int n = 0; n < NMAX; ++n) if (n == lane) v = acc[n];
-      if (p.bias) v += p.bias[lane];
-      v = head_act(v, p.tanh_);
-      const int oy = y * p.os + p.oy0[ph], ox = x * p.os + p.ox0[ph];
-      const long long off = (long long)b * p.c_bs + (long long)oy * p.c_rs + (long long)ox * p.c_ps +
-                            (long long)(p.c_co + lane) * p.c_cs;
-      if (p.out_f32) reinterpret_cast<float*>(p.c)[off] = v;
-      else st1<T>(reinterpret_cast<T*>(p.c) + off, v);
-    }
-  }
+#define STC_HALO_REMAP(iy, ix, IH, IW)
+#include "smalln.inc"
+#undef STC_HALO_REMAP
 }
+
+template <typename T>
+__global__ void __launch_bounds__(256) smalln_reflect_kernel(const ConvParams p) {
+#define STC_HALO_REMAP(iy, ix, IH, IW) iy = reflect1(iy, IH); ix = reflect1(ix, IW);
+#include "smalln.inc"
+#undef STC_HALO_REMAP
+}
+
 
 // Spatially tiled narrow-N kernel (the fast path for N <= 8).  One thread owns one
 // GEMM-grid point (all 4 sub-pixel phases for the ConvT geometry); the block stages
@@ -595,7 +321,59 @@ static void launch_narrow_tiled(int kind, int B, ConvParams& p, hipStream_t st) 
   main_timer_end(st);
 }
 
+// The fold of a reflect input gradient: frame[b][a + 1][c + 1][n] (fp32, FH x FW allocated) holds
+// what pixel (a, c) of the extended grid -1 .. H, -1 .. W receives from the padding-free transposed conv; the input
+// gradient at (y, x) is the sum over the frame pixels that reflect onto it -- its own, row -1 for y == 1, row H for
+// y == H - 2 (both for H == 3; for H == 2 row 0 takes row H and row 1 row -1), columns alike: up to 3 x 3 fp32 values
+// added in this fixed order, rounded once on store.  One thread = 4 channels of one pixel.
+template <typename T>
+__global__ void __launch_bounds__(256) reflect_fold_kernel(const float* __restrict__ frame, int FH, int FW, int N,
+                                                           int B, int H, int W, char* c, long long c_bs,
+                                                           long long c_rs, int c_ps, int c_co, int c_cs, int out_f32) {
+  const int nq = N >> 2;
+  const long long total = (long long)B * H * W * nq;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (long long)gridDim.x * blockDim.x) {
+    const int q = (int)(idx % nq);
+    long long pix = idx / nq;
+    const int x = (int)(pix % W);
+    pix /= W;
+    const int y = (int)(pix % H), b = (int)(pix / H);
+    int ry[3], rx[3], ny = 0, nx = 0;
+    ry[ny++] = y + 1;
+    if (y == 1) ry[ny++] = 0;
+    if (y == H - 2) ry[ny++] = H + 1;
+    rx[nx++] = x + 1;
+    if (x == 1) rx[nx++] = 0;
+    if (x == W - 2) rx[nx++] = W + 1;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = 0; i < ny; ++i)
+      for (int j = 0; j < nx; ++j) {
+        const float4 v = *reinterpret_cast<const float4*>(frame + (((long long)b * FH + ry[i]) * FW + rx[j]) * N + 4 * q);
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+      }
+    const long long off = (long long)b * c_bs + (long long)y * c_rs + (long long)x * c_ps;
+    const float sv[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const long long o = off + (long long)(c_co + 4 * q + e) * c_cs;
+      if (out_f32) reinterpret_cast<float*>(c)[o] = sv[e];
+      else st1<T>(reinterpret_cast<T*>(c) + o, sv[e]);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------- host
+static int launch_reflect_fold(int dtype, int B, const ConvRoute& r, int N, const stc_view& y, bool out_f32,
+                               const float* frame, hipStream_t st) {
+  const long long work = (long long)B * y.H * y.W * (N / 4);
+  STC_DT(dtype, hipLaunchKernelGGL(reflect_fold_kernel<T_>, dim3(grid_for(work)), dim3(256), 0, st, frame, r.FH, r.FW,
+                                   N, B, y.H, y.W, (char*)y.p, (long long)y.bs, (long long)y.rs, y.ps, y.co, y.cs,
+                                   (out_f32 || dtype == STC_F32) ? 1 : 0));
+  STC_CHECK_LAUNCH();
+  return 0;
+}
+
 static int ilog2_exact(int v) {
   int l = 0;
   while ((1 << l) < v) ++l;
@@ -626,14 +404,15 @@ FpPlan fp_tile_plan(int dtype, int M, int N, int K, int nphase) {
 static size_t lds_bytes(int BM, int BN) { return 2 * (size_t)(BM + BN) * LDS_ROW + BM * 8; }
 
 template <typename T>
-static int launch_igemm(const FpPlan& pl, ConvParams& p, hipStream_t st) {
+static int launch_igemm(const FpPlan& pl, ConvParams& p, hipStream_t st, bool reflect = false) {
   dim3 grid(pl.mtiles * pl.ntiles, 1, p.nphase * pl.ksplit);
   const size_t lds = lds_bytes(pl.BM, pl.BN);
   const bool pro = p.sc != nullptr || p.pro_act != 0;
   main_timer_begin(st);
 #define STC_L(BM_, BN_, WM_, WN_)                                                                  \
   if (pl.BM == BM_ && pl.BN == BN_) {                                                              \
-    if (pro) hipLaunchKernelGGL((igemm_kernel<T, BM_, BN_, WM_, WN_, true>), grid, dim3(256), lds, st, p); \
+    if (reflect) hipLaunchKernelGGL((igemm_reflect_kernel<T, BM_, BN_, WM_, WN_>), grid, dim3(256), lds, st, p); \
+    else if (pro) hipLaunchKernelGGL((igemm_kernel<T, BM_, BN_, WM_, WN_, true>), grid, dim3(256), lds, st, p); \
     else hipLaunchKernelGGL((igemm_kernel<T, BM_, BN_, WM_, WN_, false>), grid, dim3(256), lds, st, p);    \
   } else
   STC_L(128, 128, 2, 2)
@@ -770,16 +549,39 @@ static int conv_launch(const ConvAsk& a, const ConvRoute& r, const ConvOps& o) {
   for (int i = 0; i < 4; ++i) { p.oy0[i] = g.nphase == 4 ? (i >> 1) : 0; p.ox0[i] = g.nphase == 4 ? (i & 1) : 0; }
   p.bias = o.bias; p.tanh_ = a.tanh; p.out_f32 = a.out_f32 || dtype == STC_F32;
   p.nphase = g.nphase;
+  // Reflect padding.  The forward is the reflect instantiation of the kernel the route names.
+  // The input gradient is the padding-free transposed conv over the extended grid -1 .. H (r.GH x r.GW per phase):
+  // the same kernels as ever with the tap origin moved by one (frame index f = a + 1; for the stride-2 form frame
+  // row 2y + 1 is phase 0 and row 2y phase 1, both reading dy rows y - t) and an fp32 frame at the head of the
+  // workspace as the output, then reflect_fold_kernel into y.
+  const bool reflect_fwd = a.pad == STC_PAD_REFLECT && (kind == STC_CONV_S2 || kind == STC_CONV_S1);
+  const bool frame = a.pad == STC_PAD_REFLECT && !reflect_fwd;
+  char* ws = (char*)o.ws;
+  if (frame) {
+    STC_REQUIRE(o.ws && o.ws_bytes >= r.ws_bytes, "stc_conv_pad_dgrad: workspace %lld < %lld bytes",
+                (long long)o.ws_bytes, (long long)r.ws_bytes);
+    for (int i = 0; i < 4; ++i) {
+      p.offy[i] = 0; p.offx[i] = 0;
+      p.oy0[i] = g.nphase == 4 ? 1 - (i >> 1) : 0;
+      p.ox0[i] = g.nphase == 4 ? 1 - (i & 1) : 0;
+    }
+    p.c = ws; p.c_bs = (long long)r.FH * r.FW * Cout; p.c_rs = (long long)r.FW * Cout; p.c_ps = Cout; p.c_co = 0;
+    p.c_cs = 1;
+    p.bias = nullptr; p.tanh_ = 0; p.out_f32 = 1;
+    ws += r.frame_bytes;
+  }
   if (r.kernel == FP_TILE) {
     const FpPlan& pl = r.fp;
     p.ksplit = pl.ksplit; p.kchunk = pl.kchunk; p.mtiles = pl.mtiles; p.ntiles = pl.ntiles;
     if (pl.ksplit > 1) {
       STC_REQUIRE(o.ws && o.ws_bytes >= r.ws_bytes, "stc_conv_fwd: workspace %lld < %lld bytes",
                   (long long)o.ws_bytes, (long long)r.ws_bytes);
-      p.ws = (float*)o.ws;
+      p.ws = (float*)ws;
     }
-    if (dtype == STC_F32) return launch_igemm<float>(pl, p, o.st);
-    return launch_igemm<bf16>(pl, p, o.st);
+    const int rc = dtype == STC_F32 ? launch_igemm<float>(pl, p, o.st, reflect_fwd)
+                                    : launch_igemm<bf16>(pl, p, o.st, reflect_fwd);
+    if (rc || !frame) return rc;
+    return launch_reflect_fold(dtype, B, r, Cout, y, a.out_f32, (const float*)o.ws, o.st);
   }
   p.mtiles = 1; p.ntiles = 1; p.ksplit = 1; p.kchunk = K;
   STC_REQUIRE(K % (dtype == STC_F32 ? 4 : 8) == 0, "stc_conv_fwd: K=%d", K);
@@ -789,10 +591,15 @@ static int conv_launch(const ConvAsk& a, const ConvRoute& r, const ConvOps& o) {
     dim3 grid((unsigned)std::min(cdiv(p.M, 4), 4096), g.nphase);
     const size_t lds = (size_t)Cout * K * (dtype == STC_F32 ? 4 : 2);
     main_timer_begin(o.st);
-    STC_DT(dtype, hipLaunchKernelGGL(smalln_kernel<T_>, grid, dim3(256), lds, o.st, p));
+    if (reflect_fwd) {
+      STC_DT(dtype, hipLaunchKernelGGL(smalln_reflect_kernel<T_>, grid, dim3(256), lds, o.st, p));
+    } else {
+      STC_DT(dtype, hipLaunchKernelGGL(smalln_kernel<T_>, grid, dim3(256), lds, o.st, p));
+    }
     main_timer_end(o.st);
   }
   STC_CHECK_LAUNCH();
+  if (frame) return launch_reflect_fold(dtype, B, r, Cout, y, a.out_f32, (const float*)o.ws, o.st);
   return 0;
 }
 
@@ -999,3 +806,117 @@ extern "C" int stc_conv_fwd_act(int dtype, int kind, int B, stc_view x, int Cin,
   return bf16_conv_fwd(a, r, o);
 }
 
+
+// ---- Conv2d k4 p1 with a padding mode (include/stcgan_hip.h).  STC_PAD_ZEROS: the entry points
+// above, bit for bit.  STC_PAD_REFLECT: an ask with pad set -- conv_route sends it to the two gather kernels and fuses
+// nothing.  Everything is judged here, before the first launch.
+static int pad_checks(const char* who, int dtype, int kind, int pad_mode) {
+  STC_REQUIRE(dtype == STC_F32 || dtype == STC_BF16, "%s: bad dtype %d", who, dtype);
+  STC_REQUIRE(kind == STC_CONV_S2 || kind == STC_CONV_S1, "%s: kind %d is not a Conv2d kind (STC_CONV_S2, STC_CONV_S1)",
+              who, kind);
+  STC_REQUIRE(pad_mode == STC_PAD_ZEROS || pad_mode == STC_PAD_REFLECT,
+              "%s: pad_mode %d is neither STC_PAD_ZEROS nor STC_PAD_REFLECT", who, pad_mode);
+  return 0;
+}
+static int reflect_extent_check(const char* who, int H, int W) {
+  STC_REQUIRE(H >= 2 && W >= 2,
+              "%s: reflect padding needs an input extent >= 2 in both dimensions, got %d x %d (Padding size should be "
+              "less than the corresponding input dimension)", who, H, W);
+  return 0;
+}
+static int conv_out_extent(int h, int kind) { return kind == STC_CONV_S2 ? (h - 2) / 2 + 1 : h - 1; }
+static int dgrad_kind(int kind) { return kind == STC_CONV_S2 ? STC_CONVT_S2 : STC_CONV_S1_DGRAD; }
+
+extern "C" int stc_conv_pad_fwd_query(int dtype, int kind, int pad_mode, int B, int H, int W, int Cin, int Cout,
+                                      int out_f32, const int32_t* force_plan, int64_t* workspace_bytes,
+                                      int32_t* stats_chunks, int32_t* plan_out) {
+  if (const int rc = pad_checks("stc_conv_pad_fwd_query", dtype, kind, pad_mode)) return rc;
+  const int Ho = conv_out_extent(H, kind), Wo = conv_out_extent(W, kind);
+  if (pad_mode == STC_PAD_ZEROS)
+    return stc_conv_fwd_query(dtype, kind, B, Ho, Wo, Cin, Cout, out_f32, force_plan, workspace_bytes, stats_chunks,
+                              plan_out);
+  if (const int rc = reflect_extent_check("stc_conv_pad_fwd_query", H, W)) return rc;
+  STC_REQUIRE(!force_plan, "stc_conv_pad_fwd_query: no plan can be forced under STC_PAD_REFLECT (force_plan must be NULL)");
+  ConvAsk a = conv_ask(dtype, kind, B, dense_view(H, W, Cin), Cin, Cout, dense_view(Ho, Wo, Cout));
+  a.out_f32 = out_f32 != 0;
+  a.stats = true;
+  a.pad = STC_PAD_REFLECT;
+  const ConvRoute r = conv_route(a);
+  if (workspace_bytes) *workspace_bytes = r.ws_bytes;
+  if (stats_chunks) *stats_chunks = r.chunks;
+  if (plan_out)
+    for (int i = 0; i < 5; ++i) plan_out[i] = r.plan[i];
+  return 0;
+}
+
+extern "C" int stc_conv_pad_fwd(int dtype, int kind, int pad_mode, int B, stc_view x, int Cin, const void* w_packed,
+                                int Cout, stc_view y, const float* bias, int epi_tanh, int out_f32, float* stats_part,
+                                int stats_chunks, const int32_t* force_plan, void* workspace, int64_t workspace_bytes,
+                                void* stream) {
+  if (const int rc = pad_checks("stc_conv_pad_fwd", dtype, kind, pad_mode)) return rc;
+  STC_REQUIRE(x.p && w_packed && y.p, "stc_conv_pad_fwd: null operand");
+  if (pad_mode == STC_PAD_ZEROS)
+    return stc_conv_fwd_ex(dtype, kind, B, x, Cin, w_packed, Cout, y, bias, epi_tanh, out_f32, stats_part,
+                           stats_chunks, force_plan, workspace, workspace_bytes, stream);
+  STC_REQUIRE(head_code_ok(epi_tanh), "stc_conv_pad_fwd: epilogue code %d is none of STC_HEAD_* (0..3)", epi_tanh);
+  if (const int rc = reflect_extent_check("stc_conv_pad_fwd", x.H, x.W)) return rc;
+  STC_REQUIRE(!force_plan, "stc_conv_pad_fwd: no plan can be forced under STC_PAD_REFLECT (force_plan must be NULL)");
+  STC_REQUIRE(y.H == conv_out_extent(x.H, kind) && y.W == conv_out_extent(x.W, kind),
+              "stc_conv_pad_fwd: y %d x %d is not the k4 s%d p1 output of x %d x %d", y.H, y.W,
+              kind == STC_CONV_S2 ? 2 : 1, x.H, x.W);
+  ConvAsk a = conv_ask(dtype, kind, B, x, Cin, Cout, y);
+  a.tanh = epi_tanh; a.out_f32 = out_f32 != 0; a.stats = stats_part != nullptr; a.pad = STC_PAD_REFLECT;
+  ConvOps o{};
+  o.w = w_packed; o.bias = bias; o.ws = workspace; o.ws_bytes = workspace_bytes; o.st = (hipStream_t)stream;
+  if (const int rc = conv_fwd_checks(a, o)) return rc;
+  const ConvRoute r = conv_route(a);
+  STC_REQUIRE(!stats_part || !a.out_f32 || dtype == STC_F32, "stc_conv_pad_fwd: stats of a non-activation output");
+  STC_REQUIRE(r.ws_bytes == 0 || (workspace && workspace_bytes >= r.ws_bytes),
+              "stc_conv_pad_fwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)r.ws_bytes);
+  const int rc = conv_launch(a, r, o);
+  if (rc != 0 || stats_part == nullptr) return rc;
+  return stc_chan_stats(dtype, B, y, Cout, stats_part, stats_chunks, (hipStream_t)stream);
+}
+
+extern "C" int stc_conv_pad_dgrad_query(int dtype, int kind, int pad_mode, int B, int H, int W, int Cout, int Cin,
+                                        int out_f32, int64_t* workspace_bytes, int32_t* plan_out) {
+  if (const int rc = pad_checks("stc_conv_pad_dgrad_query", dtype, kind, pad_mode)) return rc;
+  const int Ho = conv_out_extent(H, kind), Wo = conv_out_extent(W, kind);
+  if (pad_mode == STC_PAD_ZEROS)  // (the grid of STC_CONVT_S2 is its input dy, of STC_CONV_S1_DGRAD its output dx)
+    return stc_conv_fwd_query(dtype, dgrad_kind(kind), B, kind == STC_CONV_S2 ? Ho : H, kind == STC_CONV_S2 ? Wo : W,
+                              Cout, Cin, out_f32, nullptr, workspace_bytes, nullptr, plan_out);
+  if (const int rc = reflect_extent_check("stc_conv_pad_dgrad_query", H, W)) return rc;
+  ConvAsk a = conv_ask(dtype, dgrad_kind(kind), B, dense_view(Ho, Wo, Cout), Cout, Cin, dense_view(H, W, Cin));
+  a.out_f32 = out_f32 != 0;
+  a.pad = STC_PAD_REFLECT;
+  const ConvRoute r = conv_route(a);
+  if (workspace_bytes) *workspace_bytes = r.ws_bytes;
+  if (plan_out)
+    for (int i = 0; i < 5; ++i) plan_out[i] = r.plan[i];
+  return 0;
+}
+
+extern "C" int stc_conv_pad_dgrad(int dtype, int kind, int pad_mode, int B, stc_view dy, int Cout, const void* w_packed,
+                                  int Cin, stc_view dx, int out_f32, void* workspace, int64_t workspace_bytes,
+                                  void* stream) {
+  if (const int rc = pad_checks("stc_conv_pad_dgrad", dtype, kind, pad_mode)) return rc;
+  STC_REQUIRE(dy.p && w_packed && dx.p, "stc_conv_pad_dgrad: null operand");
+  if (pad_mode == STC_PAD_ZEROS)
+    return stc_conv_fwd_ex(dtype, dgrad_kind(kind), B, dy, Cout, w_packed, Cin, dx, nullptr, 0, out_f32, nullptr, 0,
+                           nullptr, workspace, workspace_bytes, stream);
+  if (const int rc = reflect_extent_check("stc_conv_pad_dgrad", dx.H, dx.W)) return rc;
+  STC_REQUIRE(dy.H == conv_out_extent(dx.H, kind) && dy.W == conv_out_extent(dx.W, kind),
+              "stc_conv_pad_dgrad: dy %d x %d is not the k4 s%d p1 output of dx %d x %d", dy.H, dy.W,
+              kind == STC_CONV_S2 ? 2 : 1, dx.H, dx.W);
+  STC_REQUIRE(Cin >= 4 && Cin % 4 == 0, "stc_conv_pad_dgrad: Cin=%d must be a multiple of 4", Cin);
+  ConvAsk a = conv_ask(dtype, dgrad_kind(kind), B, dy, Cout, Cin, dx);
+  a.out_f32 = out_f32 != 0;
+  a.pad = STC_PAD_REFLECT;
+  ConvOps o{};
+  o.w = w_packed; o.ws = workspace; o.ws_bytes = workspace_bytes; o.st = (hipStream_t)stream;
+  if (const int rc = conv_fwd_checks(a, o)) return rc;
+  const ConvRoute r = conv_route(a);
+  STC_REQUIRE(workspace && workspace_bytes >= r.ws_bytes, "stc_conv_pad_dgrad: workspace %lld < %lld bytes",
+              (long long)workspace_bytes, (long long)r.ws_bytes);
+  return conv_launch(a, r, o);
+}

@@ -97,180 +97,23 @@ __device__ __forceinline__ v4i16 lds_tr16(const char* p) {
 template <typename T>
 __global__ void __launch_bounds__(256)
 wgrad_kernel(const WgradParams p) {
-  constexpr int VEC = 16 / sizeof(T);
-  constexpr int CPR = WG_BM * (int)sizeof(T) / 16;  // 16-byte chunks per staged row (32 fp32 / 16 bf16)
-  constexpr int RPP = 256 / CPR;                     // rows per pass
-  constexpr int NP = WG_BK / RPP;                    // passes per K-step (4 fp32 / 2 bf16)
-  constexpr int ROWB = WgCfg<T>::ROWB;
-  constexpr int TILEB = WG_BK * ROWB;
-  __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILEB];  // [stage][A|B]
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int nwg = p.mtiles * p.ntiles;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int mt = bid / p.ntiles, nt = bid % p.ntiles;
-  const int r0 = mt * WG_BM, c0 = nt * WG_BN;
-  const int split = blockIdx.z;
-  const int pbeg = split * p.pchunk;
-  const int pend = min(p.P, pbeg + p.pchunk);
-  const int GHW = p.GH * p.GW;
-
-  // staging map: row (pixel) kp = tid/CPR + RPP*i, chunk = tid%CPR (VEC channels)
-  const int chunk = tid % CPR;
-  const int rr = r0 + chunk * VEC;   // D channel of this chunk
-  const int col = c0 + chunk * VEC;  // G column of this chunk
-  const bool rval = rr < p.R;
-  const bool cval = col < p.Ncol;
-  const int t = col / p.Cg, ci = col - t * p.Cg;
-  const int kh = t >> 2, kw = t & 3;
-  const T* Dp = reinterpret_cast<const T*>(p.d);
-  const T* Gp = reinterpret_cast<const T*>(p.g);
-  const float* dsc = p.dsc ? p.dsc + rr : nullptr;
-  const float* dsh = p.dsh ? p.dsh + rr : nullptr;
-  const float* gsc = p.gsc ? p.gsc + ci : nullptr;
-  const float* gsh = p.gsh ? p.gsh + ci : nullptr;
-  const bool dpro = p.dsc != nullptr || p.dact;
-  const bool gpro = p.gsc != nullptr || p.gact;
-
-  uint4 va[NP], vb[NP];
-  unsigned ma = 0, mb = 0;
-  auto load = [&](int k0) {
-    ma = 0; mb = 0;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int pix = k0 + tid / CPR + RPP * i;
-      va[i] = make_uint4(0, 0, 0, 0);
-      vb[i] = make_uint4(0, 0, 0, 0);
-      if (pix < pend) {
-        const int b = pix / GHW, rem = pix - b * GHW;
-        const int oy = rem / p.GW, ox = rem - oy * p.GW;
-        if (rval) {
-          va[i] = *reinterpret_cast<const uint4*>(Dp + (long long)b * p.d_bs + (long long)oy * p.d_rs +
-                                                  (long long)ox * p.d_ps + p.d_co + rr);
-          ma |= 1u << i;
-        }
-        const int iy = oy * p.stride + kh - 1, ix = ox * p.stride + kw - 1;
-        if (cval && (unsigned)iy < (unsigned)p.IH && (unsigned)ix < (unsigned)p.IW) {
-          vb[i] = *reinterpret_cast<const uint4*>(Gp + (long long)b * p.g_bs + (long long)iy * p.g_rs +
-                                                  (long long)ix * p.g_ps + p.g_co + ci);
-          mb |= 1u << i;
-        }
-      }
-    }
-  };
-  auto store = [&](int st) {
-    char* sA = smem + st * 2 * TILEB;
-    char* sB = sA + TILEB;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int kp = tid / CPR + RPP * i;
-      uint4 a = va[i], b = vb[i];
-      if (dpro && (ma >> i & 1u)) a = wg_pro<T>(a, dsc, dsh, p.dact, p.dslope);
-      if (gpro && (mb >> i & 1u)) b = wg_pro<T>(b, gsc, gsh, p.gact, p.gslope);
-      *reinterpret_cast<uint4*>(sA + kp * ROWB + chunk * 16) = a;
-      *reinterpret_cast<uint4*>(sB + kp * ROWB + chunk * 16) = b;
-    }
-  };
-
-  floatx16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  const int nsteps = (pend - pbeg + WG_BK - 1) / WG_BK;
-  if (nsteps > 0) {
-    load(pbeg);
-    store(0);
-  }
-  __syncthreads();
-  const int li = lane & 31, lh = lane >> 5;
-  // transposed-read addressing (bf16): 16-lane group g16, lane-in-group 4*trq + trp
-  const int g16 = lane >> 4, lig = lane & 15;
-  const int trq = lig >> 2, trp = lig & 3;
-  const int trh = g16 >> 1, trc = 16 * (g16 & 1) + 4 * trp;
-  for (int s = 0; s < nsteps; ++s) {
-    const int cur = s & 1;
-    if (s + 1 < nsteps) load(pbeg + (s + 1) * WG_BK);
-    const char* sA = smem + cur * 2 * TILEB;
-    const char* sB = sA + TILEB;
-    if constexpr (sizeof(T) == 4) {
-#pragma unroll 4
-      for (int kk = 0; kk < WG_BK / 2; ++kk) {
-        const int k = 2 * kk + lh;
-        const float* ra = reinterpret_cast<const float*>(sA + k * ROWB);
-        const float* rb = reinterpret_cast<const float*>(sB + k * ROWB);
-        const float a0 = ra[wm * 64 + li], a1 = ra[wm * 64 + 32 + li];
-        const float b0 = rb[wn * 64 + li], b1 = rb[wn * 64 + 32 + li];
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-      }
-    } else {
-#pragma unroll
-      for (int ks = 0; ks < WG_BK / 16; ++ks) {
-        bf16x8 fa[2], fb[2];
-        const int row = ks * 16 + 8 * trh + trq;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const char* pa = sA + row * ROWB + (wm * 64 + 32 * i + trc) * 2;
-          const char* pb = sB + row * ROWB + (wn * 64 + 32 * i + trc) * 2;
-          const v4i16 a_lo = lds_tr16(pa), a_hi = lds_tr16(pa + 4 * ROWB);
-          const v4i16 b_lo = lds_tr16(pb), b_hi = lds_tr16(pb + 4 * ROWB);
-          const v8i16 av = {a_lo[0], a_lo[1], a_lo[2], a_lo[3], a_hi[0], a_hi[1], a_hi[2], a_hi[3]};
-          const v8i16 bv = {b_lo[0], b_lo[1], b_lo[2], b_lo[3], b_hi[0], b_hi[1], b_hi[2], b_hi[3]};
-          fa[i] = __builtin_bit_cast(bf16x8, av);
-          fb[i] = __builtin_bit_cast(bf16x8, bv);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-      }
-    }
-    if (s + 1 < nsteps) store(cur ^ 1);
-    __syncthreads();
-  }
-
-  if (p.dW) {  // single pixel split: write torch layout dW[r][ci][kh][kw] directly
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = c0 + wn * 64 + 32 * j + li;
-      const int tt = n / p.Cg, cc = n - tt * p.Cg;
-      if (n >= p.Ncol || cc >= p.Cg_out) continue;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int m = r0 + wm * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * lh;
-          if (m < p.R) p.dW[((long long)m * p.Cg_out + cc) * 16 + tt] = acc[i][j][e];
-        }
-    }
-    return;
-  }
-  float* slab = p.ws + (long long)split * p.R * p.Ncol;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = c0 + wn * 64 + 32 * j + li;
-      if (n >= p.Ncol) continue;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = r0 + wm * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * lh;
-        if (m < p.R) slab[(long long)m * p.Ncol + n] = acc[i][j][e];
-      }
-    }
+#define STC_HALO_REMAP(iy, ix, IH, IW)
+#include "wgrad_tile.inc"
+#undef STC_HALO_REMAP
 }
+
+// the same kernel with the reflected halo of G (STC_PAD_REFLECT: G row -1 reads row 1, row IH reads row IH - 2;
+// DESIGN.md section 8i) -- a remap of the gather index, nothing else
+template <typename T>
+__global__ void __launch_bounds__(256)
+wgrad_reflect_kernel(const WgradParams p) {
+#define STC_HALO_REMAP(iy, ix, IH, IW) \
+  iy = iy == -1 ? 1 : (iy == IH ? IH - 2 : iy); \
+  ix = ix == -1 ? 1 : (ix == IW ? IW - 2 : ix);
+#include "wgrad_tile.inc"
+#undef STC_HALO_REMAP
+}
+
 
 // dW[r][ci][kh][kw] = sum_s ws[s][r][(kh*4+kw)*Cg + ci]: one thread per (r, tap, ci) with ci fastest
 // (coalesced slab reads), the splits summed in a fixed order with 4 independent partial sums.
@@ -449,6 +292,16 @@ void wgrad_reduce_launch(const float* ws, int nsplit, int R, int Cg, int Cg_out,
   else
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)wgrad_reduce_blocks(R, Cg_out)), dim3(128), 0, st, ws,
                        nsplit, R, Cg, Cg_out, dW);
+}
+
+static void wgrad_launch(int dtype, int pad, dim3 grid, const WgradParams& p, hipStream_t st) {
+  if (pad) {
+    if (dtype == STC_F32) hipLaunchKernelGGL(wgrad_reflect_kernel<float>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(wgrad_reflect_kernel<bf16>, grid, dim3(256), 0, st, p);
+  } else {
+    if (dtype == STC_F32) hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(wgrad_kernel<bf16>, grid, dim3(256), 0, st, p);
+  }
 }
 
 struct WgPlan {
@@ -788,12 +641,13 @@ extern "C" int stc_conv_wgrad(int dtype, int B, int stride, stc_view D, int R,
                            g_act, g_slope, dW, nullptr, workspace, workspace_bytes, stream);
 }
 
-extern "C" int stc_conv_wgrad_ex(int dtype, int B, int stride, stc_view D, int R,
-                                 const float* d_scale, const float* d_shift, int d_act, float d_slope,
-                                 stc_view G, int Cg, int Cg_out,
-                                 const float* g_scale, const float* g_shift, int g_act, float g_slope,
-                                 float* dW, const int32_t* force_plan, void* workspace, int64_t workspace_bytes,
-                                 void* stream) {
+// pad: STC_PAD_ZEROS, or STC_PAD_REFLECT -- the register-staged kernel's reflect instantiation, whatever the dtype
+static int wgrad_run(int dtype, int B, int stride, stc_view D, int R,
+                     const float* d_scale, const float* d_shift, int d_act, float d_slope,
+                     stc_view G, int Cg, int Cg_out,
+                     const float* g_scale, const float* g_shift, int g_act, float g_slope,
+                     float* dW, const int32_t* force_plan, void* workspace, int64_t workspace_bytes,
+                     void* stream, int pad) {
   STC_REQUIRE(dtype == STC_F32 || dtype == STC_BF16, "stc_conv_wgrad: bad dtype");
   const int VEC = dtype == STC_F32 ? 4 : 8;
   STC_REQUIRE(Cg >= VEC && Cg % VEC == 0, "stc_conv_wgrad: Cg=%d must be a multiple of %d", Cg, VEC);
@@ -815,7 +669,7 @@ extern "C" int stc_conv_wgrad_ex(int dtype, int B, int stride, stc_view D, int R
     STC_CHECK_LAUNCH();
     return 0;
   }
-  if (dtype == STC_BF16 && !d_scale && !d_act && !g_scale && !g_act && wgrad_bf16_eligible(B, D, R, G, Cg))
+  if (!pad && dtype == STC_BF16 && !d_scale && !d_act && !g_scale && !g_act && wgrad_bf16_eligible(B, D, R, G, Cg))
     return wgrad_bf16(B, stride, D, R, G, Cg, Cg_out, dW, workspace, workspace_bytes, st, force_plan);
   const WgPlan pl = wg_plan(p.P, R, Cg);
   p.mtiles = pl.mtiles; p.ntiles = pl.ntiles; p.nsplit = pl.nsplit; p.pchunk = pl.pchunk;
@@ -824,8 +678,7 @@ extern "C" int stc_conv_wgrad_ex(int dtype, int B, int stride, stc_view D, int R
   if (pl.nsplit <= 1) {
     p.dW = dW;
     main_timer_begin(st);
-    if (dtype == STC_F32) hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(wgrad_kernel<bf16>, grid, dim3(256), 0, st, p);
+    wgrad_launch(dtype, pad, grid, p, st);
     main_timer_end(st);
     STC_CHECK_LAUNCH();
     return 0;
@@ -835,11 +688,64 @@ extern "C" int stc_conv_wgrad_ex(int dtype, int B, int stride, stc_view D, int R
               (long long)workspace_bytes, (long long)need);
   p.ws = (float*)workspace;
   main_timer_begin(st);
-  if (dtype == STC_F32) hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), 0, st, p);
-  else hipLaunchKernelGGL(wgrad_kernel<bf16>, grid, dim3(256), 0, st, p);
+  wgrad_launch(dtype, pad, grid, p, st);
   main_timer_end(st);
   STC_CHECK_LAUNCH();
   wgrad_reduce_launch((const float*)p.ws, pl.nsplit, R, Cg, Cg_out, dW, st);
   STC_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int stc_conv_wgrad_ex(int dtype, int B, int stride, stc_view D, int R,
+                                 const float* d_scale, const float* d_shift, int d_act, float d_slope,
+                                 stc_view G, int Cg, int Cg_out,
+                                 const float* g_scale, const float* g_shift, int g_act, float g_slope,
+                                 float* dW, const int32_t* force_plan, void* workspace, int64_t workspace_bytes,
+                                 void* stream) {
+  return wgrad_run(dtype, B, stride, D, R, d_scale, d_shift, d_act, d_slope, G, Cg, Cg_out, g_scale, g_shift, g_act,
+                   g_slope, dW, force_plan, workspace, workspace_bytes, stream, STC_PAD_ZEROS);
+}
+
+// ---- weight gradient of a Conv2d with a padding mode.  STC_PAD_ZEROS: stc_conv_wgrad_ex /
+// stc_conv_wgrad_query themselves.  STC_PAD_REFLECT: the same GEMM with the G operand (the conv's input) gathered
+// through the reflect map, on the register-staged kernel; arguments are judged before anything is launched.
+static int pad_wgrad_checks(const char* who, int dtype, int kind, int pad_mode, const int32_t* force_plan) {
+  STC_REQUIRE(dtype == STC_F32 || dtype == STC_BF16, "%s: bad dtype %d", who, dtype);
+  STC_REQUIRE(kind == STC_CONV_S2 || kind == STC_CONV_S1, "%s: kind %d is not a Conv2d kind (STC_CONV_S2, STC_CONV_S1)",
+              who, kind);
+  STC_REQUIRE(pad_mode == STC_PAD_ZEROS || pad_mode == STC_PAD_REFLECT,
+              "%s: pad_mode %d is neither STC_PAD_ZEROS nor STC_PAD_REFLECT", who, pad_mode);
+  STC_REQUIRE(pad_mode == STC_PAD_ZEROS || !force_plan,
+              "%s: no plan can be forced under STC_PAD_REFLECT (force_plan must be NULL)", who);
+  return 0;
+}
+
+extern "C" int stc_conv_pad_wgrad_query(int dtype, int kind, int pad_mode, int B, int Hd, int Wd, int R, int Cg,
+                                        const int32_t* force_plan, int64_t* workspace_bytes, int32_t* plan_out) {
+  if (const int rc = pad_wgrad_checks("stc_conv_pad_wgrad_query", dtype, kind, pad_mode, force_plan)) return rc;
+  if (pad_mode == STC_PAD_ZEROS)
+    return stc_conv_wgrad_query(dtype, B, Hd, Wd, R, Cg, force_plan, workspace_bytes, plan_out);
+  const WgPlan pl = wg_plan(B * Hd * Wd, R, Cg);
+  if (workspace_bytes) *workspace_bytes = pl.nsplit <= 1 ? 0 : (int64_t)pl.nsplit * R * 16LL * Cg * 4;
+  if (plan_out) {
+    plan_out[0] = -1; plan_out[1] = WG_BM; plan_out[2] = WG_BN; plan_out[3] = pl.nsplit; plan_out[4] = pl.nsplit > 1;
+  }
+  return 0;
+}
+
+extern "C" int stc_conv_pad_wgrad(int dtype, int kind, int pad_mode, int B, stc_view dy, int R, stc_view x, int Cg,
+                                  int Cg_out, float* dW, const int32_t* force_plan, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+  if (const int rc = pad_wgrad_checks("stc_conv_pad_wgrad", dtype, kind, pad_mode, force_plan)) return rc;
+  STC_REQUIRE(dy.p && x.p && dW, "stc_conv_pad_wgrad: null operand");
+  const int stride = kind == STC_CONV_S2 ? 2 : 1;
+  if (pad_mode == STC_PAD_REFLECT) {
+    STC_REQUIRE(x.H >= 2 && x.W >= 2,
+                "stc_conv_pad_wgrad: reflect padding needs an input extent >= 2 in both dimensions, got %d x %d "
+                "(Padding size should be less than the corresponding input dimension)", x.H, x.W);
+    STC_REQUIRE(dy.H == (x.H - 2) / stride + 1 && dy.W == (x.W - 2) / stride + 1,
+                "stc_conv_pad_wgrad: dy %d x %d is not the k4 s%d p1 output of x %d x %d", dy.H, dy.W, stride, x.H, x.W);
+  }
+  return wgrad_run(dtype, B, stride, dy, R, nullptr, nullptr, 0, 0.f, x, Cg, Cg_out, nullptr, nullptr, 0, 0.f, dW,
+                   force_plan, workspace, workspace_bytes, stream, pad_mode);
 }

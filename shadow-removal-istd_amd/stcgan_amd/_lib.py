@@ -23,6 +23,11 @@ HEAD_NONE, HEAD_TANH, HEAD_SIGMOID, HEAD_HTANH = 0, 1, 2, 3
 HEADS = {"none": HEAD_NONE, "tanh": HEAD_TANH, "sigmoid": HEAD_SIGMOID, "htanh": HEAD_HTANH}
 
 
+# STC_PAD_*: the padding mode of a Conv2d k4 p1 (stc_conv_pad_fwd / _dgrad / _wgrad)
+PAD_ZEROS, PAD_REFLECT = 0, 1
+PADS = {"zeros": PAD_ZEROS, "reflect": PAD_REFLECT}
+
+
 def head_code(act):
     """The STC_HEAD_* code of an output head name ("none" / None, "tanh", "sigmoid", "htanh"); an int is passed
     through for the library to judge."""
@@ -109,6 +114,13 @@ _SIGS = {
     "stc_conv_wgrad_ex": (_i32, [_i32, _i32, _i32, View, _i32, _vp, _vp, _i32, _f32, View, _i32, _i32, _vp, _vp, _i32,
                                  _f32, _vp, _vp, _vp, _i64, _vp]),
     "stc_conv_wgrad_query": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "stc_conv_pad_fwd": (_i32, [_i32, _i32, _i32, _i32, View, _i32, _vp, _i32, View, _vp, _i32, _i32, _vp, _i32, _vp,
+                                _vp, _i64, _vp]),
+    "stc_conv_pad_fwd_query": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "stc_conv_pad_dgrad": (_i32, [_i32, _i32, _i32, _i32, View, _i32, _vp, _i32, View, _i32, _vp, _i64, _vp]),
+    "stc_conv_pad_dgrad_query": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "stc_conv_pad_wgrad": (_i32, [_i32, _i32, _i32, _i32, View, _i32, View, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "stc_conv_pad_wgrad_query": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "stc_pack_weight": (_i32, [_i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
     "stc_pack_weights": (_i32, [_i32, _i32, _vp, _vp]),
     "stc_upconv_expand": (_i32, [_vp, _i32, _i32, _vp, _vp]),

@@ -281,6 +281,10 @@ class GenPlan:
         # {level k: p}: train-mode dropout on the output of BN_up[k] (the blocks right above the innermost one)
         self.drop = drop
         self.co = [c.out_channels for c in conv]
+        # the padding mode of each down conv (L.PAD_ZEROS / L.PAD_REFLECT), read from the module as torch would run it:
+        # a reflect layer takes the reflect kernels and the unfused step forms
+        self.conv_names = [names.get(id(c), "?") for c in conv]
+        self.pad = [_pad_of(c, n) for c, n in zip(conv, self.conv_names)]
         # which norm the network uses: BatchNorm2d, or InstanceNorm2d (affine or not)
         self.inorm, self.affine = _norm_kind(list(bnd.values()) + list(bnu.values()))
         self.sync, self.norm_names = _sync_kind(list(bnd.values()) + list(bnu.values()), names)
@@ -305,6 +309,21 @@ def _head_of(seq, name):
     what = repr(m) if m is not None else "more than one module after the up layer"
     raise NotImplementedError(f"stcgan_amd: output activation {where}: {what} is not supported -- nothing (none), "
                               "nn.Tanh, nn.Sigmoid or nn.Hardtanh(-1.0, 1.0)")
+
+
+def _pad_of(conv, name):
+    """L.PAD_ZEROS / L.PAD_REFLECT of a 4x4 nn.Conv2d; "replicate" and "circular" have no kernel."""
+    if conv.padding_mode not in L.PADS:
+        raise NotImplementedError(f"stcgan_amd: conv layer {name}: padding_mode={conv.padding_mode!r} is not supported "
+                                  "('zeros' or 'reflect')")
+    return L.PADS[conv.padding_mode]
+
+
+def _check_reflect_plane(name, B, C, h, w):
+    """torch's refusal of a reflect pad as wide as the plane (ReflectionPad2d), before any launch."""
+    if h < 2 or w < 2:
+        raise RuntimeError(f"stcgan_amd: conv layer {name} (padding_mode='reflect'): Padding size should be less than "
+                           f"the corresponding input dimension, but got: padding (1, 1) of input [{B}, {C}, {h}, {w}]")
 
 
 def _up_layer(m, name):
@@ -414,7 +433,7 @@ class _Sync:
 
 
 def _conv_norm_act(kind, B, xv, cin, w, cout, yv, dt, norm, mode, apply_x, y1, s1, y2, s2, drop, defer, keep,
-                   sync=None):
+                   sync=None, pad=L.PAD_ZEROS):
     """Conv into ``yv`` -> norm layer ``norm`` -> activation pass of ``apply_x`` (yv or its top-left crop) into y1 [and
     y2] (y1 None: no pass).  Returns ((2, cout) scale / shift table or None, (mean, rstd) or None).
     _BATCH: one library call, the statistics out of the conv itself; ``defer`` (a list): the running statistics are not
@@ -422,13 +441,15 @@ def _conv_norm_act(kind, B, xv, cin, w, cout, yv, dt, norm, mode, apply_x, y1, s
     statistics, the apply pass; ``keep`` (a backward will follow): (running_mean, rstd_run) beside the table.  _IN:
     conv, then the statistics of the stored raw output with the pass; no table.  ``drop``: a dropout level between a
     BatchNorm and the activation (dropout_next).  _SYNC (``sync``: the call's _Sync): the split form of _BATCH with
-    one gather of the ranks' records between the partials and the table; ``defer`` gets the gathered records."""
+    one gather of the ranks' records between the partials and the table; ``defer`` gets the gathered records.
+    pad=L.PAD_REFLECT: the same forms around the reflect conv; _BATCH then takes its three separate calls (the
+    statistics from a pass over the stored output)."""
     if mode == _SYNC:
         return ops.conv_bn_act_sync(kind, B, xv, cin, w, cout, yv, dt, norm, apply_x, y1, s1, y2, s2, defer, drop,
-                                    sync.gather(norm, "forward"))
+                                    sync.gather(norm, "forward"), pad)
     if mode == _BATCH:
-        return ops.conv_bn_act(kind, B, xv, cin, w, cout, yv, dt, norm, apply_x, y1, s1, y2, s2, defer, drop)
-    ops.conv(kind, B, xv, cin, w, cout, yv, dt)
+        return ops.conv_bn_act(kind, B, xv, cin, w, cout, yv, dt, norm, apply_x, y1, s1, y2, s2, defer, drop, pad)
+    ops.conv(kind, B, xv, cin, w, cout, yv, dt, pad=pad)
     if mode == _IN:
         return None, ops.in_forward(B, yv, cout, dt, norm, apply_x, y1, s1, y2, s2)
     t = torch.empty((2, cout), dtype=torch.float32, device=w.device)
@@ -440,7 +461,7 @@ def _conv_norm_act(kind, B, xv, cin, w, cout, yv, dt, norm, mode, apply_x, y1, s
 
 
 def _conv_act_norm_backward(kind, B, gv, cg, wd, cin, gt, yv, dt, norm, mode, tab, st, xv, C, s_self, g_other, s_other,
-                            ch_off, dxv, drop, own, W, lane, sync=None):
+                            ch_off, dxv, drop, own, W, lane, sync=None, pad=L.PAD_ZEROS):
     """The backward of one layer boundary: the input-gradient conv (kind, gv with cg channels, packed weight wd, cin
     output channels) into the view ``yv`` of tensor ``gt``, then the backward of the activation(s) and of the norm
     layer ``norm`` (None: none) that produced the conv's input, into ``dxv``.  xv: the norm's input (C channels),
@@ -456,20 +477,22 @@ def _conv_act_norm_backward(kind, B, gv, cg, wd, cin, gt, yv, dt, norm, mode, ta
     _RUNNING               conv, bn_backward_frozen (through ``drop`` where there is one)
     _BATCH with ``drop``   conv, bn_backward (the GEMM epilogues know nothing of the mask)
     _BATCH                 the BatchNorm reduction fused into the conv (conv_bn_backward)
-    _SYNC                  as _BATCH, in the split forms with one gather of the ranks' sums before the apply"""
+    _SYNC                  as _BATCH, in the split forms with one gather of the ranks' sums before the apply
+    pad=L.PAD_REFLECT (the conv whose input gradient this is pads by reflection): the reflect input gradient -- frame
+    and fold -- and always the unfused forms: a fused epilogue would form its sums before the fold."""
     if norm is None:
         # (no epilogue form under TRACE, which wants the conv's own output, or where the conv writes a larger extent
         # than the activation's: an odd generator level)
-        if (TRACE is None and yv.H == xv.H and yv.W == xv.W
+        if (TRACE is None and pad == L.PAD_ZEROS and yv.H == xv.H and yv.W == xv.W
                 and ops.conv_act_backward(kind, B, gv, cg, wd, cin, dxv, dt, xv, s_self, g_other, s_other)):
             if W is not None:
                 W.done(own, lane)
             return
         fused = False
     else:
-        fused = mode in (_BATCH, _SYNC) and drop is None
+        fused = mode in (_BATCH, _SYNC) and drop is None and pad == L.PAD_ZEROS
     if not fused:
-        ops.conv(kind, B, gv, cg, wd, cin, yv, dt)
+        ops.conv(kind, B, gv, cg, wd, cin, yv, dt, pad=pad)
         if W is not None and norm is not None:
             W.done(own, lane)
         # the kernels form g1 * act1' + g2 * act2' in this order: another consumer's gradient first
@@ -511,13 +534,14 @@ def _conv_act_norm_backward(kind, B, gv, cg, wd, cin, gt, yv, dt, norm, mode, ta
         W.done([norm.weight, norm.bias])
 
 
-def _input_grads(B, gv, cg, weight, saved, hw, need_src, dt, cache, dev):
+def _input_grads(B, gv, cg, weight, saved, hw, need_src, dt, cache, dev, pad=L.PAD_ZEROS):
     """The tail of a backward: the first layer's input-gradient conv (gradient view gv, cg channels) into a padded
     NHWC tensor, scattered into one NCHW fp32 gradient per source that needs one (None for the others)."""
     cin_pad = saved["cin_pad"]
     wd = ops.packed(cache, weight, L.PACK_CONV_DGRAD, cin_pad, cg, dt)
-    gx = _nhwc(B, 2 * gv.H, 2 * gv.W, cin_pad, dt, dev)
-    ops.conv(L.CONVT_S2, B, gv, cg, wd, cin_pad, L.nhwc_view(gx), dt)
+    # (zeros: the ConvT geometry writes 2 * gv.H rows; reflect: the fold writes the input's own extent, odd or even)
+    gx = _nhwc(B, *(hw if pad != L.PAD_ZEROS else (2 * gv.H, 2 * gv.W)), cin_pad, dt, dev)
+    ops.conv(L.CONVT_S2, B, gv, cg, wd, cin_pad, L.nhwc_view(gx), dt, pad=pad)
     H, W_ = hw
     # only the sources that need a gradient; the scatter writes every element of those
     src_grads = [torch.empty((B, c, H, W_), dtype=torch.float32, device=dev) if nd else None
@@ -544,6 +568,17 @@ def gen_forward(plan, sources, train, dt, cache, save, batch_stats=None):
     if plan.inorm:
         for k in range(1, Lv - 1):
             _check_plane(B, co[k], *S[k + 1])
+    for k in range(Lv):  # conv_k reads the S[k] plane
+        if plan.pad[k] != L.PAD_REFLECT:
+            continue
+        name = plan.conv_names[k]
+        _check_reflect_plane(name, B, cin if k == 0 else co[k - 1], *S[k])
+        if S[k][0] % 2 or S[k][1] % 2:
+            # (the reference tree zero-pads an odd level to even and reflects about the padded extent: not built)
+            raise NotImplementedError(
+                f"stcgan_amd: generator level {k} ({name}, padding_mode='reflect') reads an odd {S[k][0]} x {S[k][1]} "
+                f"plane for a {H} x {W} input: reflect padding needs every level even (H and W multiples of "
+                f"{2 ** (Lv - 1)} here)")
     cin_pad = ops.pad_channels(cin, dt)
     xin = _nhwc(B, H, W, cin_pad, dt, dev)
     ops.gather(sources, xin, dt)
@@ -572,13 +607,13 @@ def gen_forward(plan, sources, train, dt, cache, save, batch_stats=None):
     # ---- down path
     w0 = ops.packed(cache, plan.conv[0].weight, L.PACK_CONV_FWD, co[0], cin_pad, dt)
     xv, av, sv = L.nhwc_view(xin), L.nhwc_view(ad[0]), L.nhwc_view(cr[0], 0)  # conv input, its activation, the skip
-    if ops.conv_act(L.CONV_S2, B, xv, cin_pad, w0, co[0], av, LRELU, dt, sv, 0.0):
+    if plan.pad[0] == L.PAD_ZEROS and ops.conv_act(L.CONV_S2, B, xv, cin_pad, w0, co[0], av, LRELU, dt, sv, 0.0):
         # no raw r_0: its only reader, the backward's ReLU/LeakyReLU test, sees the same signs in ad[0]
         rd[0] = ad[0]
     else:
         rd[0] = _nhwc(B, *S[1], co[0], dt, dev)
         rv = L.nhwc_view(rd[0])
-        ops.conv(L.CONV_S2, B, xv, cin_pad, w0, co[0], rv, dt)
+        ops.conv(L.CONV_S2, B, xv, cin_pad, w0, co[0], rv, dt, pad=plan.pad[0])
         ops.bn_apply(B, rv, co[0], dt, None, av, LRELU, sv, 0.0)
     for k in range(1, Lv):
         wk = ops.packed(cache, plan.conv[k].weight, L.PACK_CONV_FWD, co[k], co[k - 1], dt)
@@ -586,11 +621,11 @@ def gen_forward(plan, sources, train, dt, cache, save, batch_stats=None):
         if k <= Lv - 2:
             av = L.nhwc_view(ad[k])
             t, st_d[k] = _conv_norm_act(L.CONV_S2, B, xv, co[k - 1], wk, co[k], rv, dt, plan.bnd[k], mode, rv, av,
-                                        LRELU, L.nhwc_view(cr[k], 0), 0.0, None, None, save, sync)
+                                        LRELU, L.nhwc_view(cr[k], 0), 0.0, None, None, save, sync, plan.pad[k])
             if t is not None:
                 tab_d[k] = t
         else:  # innermost: no down-norm (STCGAN/networks.py:118-124)
-            ops.conv(L.CONV_S2, B, xv, co[k - 1], wk, co[k], rv, dt)
+            ops.conv(L.CONV_S2, B, xv, co[k - 1], wk, co[k], rv, dt, pad=plan.pad[k])
             ops.bn_apply(B, rv, co[k], dt, None, L.nhwc_view(cr[k]), 0.0)
     # ---- up path
     for k in range(Lv - 1, 0, -1):
@@ -698,17 +733,17 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
             if need_w:
                 out = W.dest(wk)
                 lane.run(lambda: ops.wgrad(B, 2, drv, co[0], L.nhwc_view(xin), saved["cin_pad"], saved["cin"], dt,
-                                           device=dev, out=out), dr, pixels=S[1][0] * S[1][1])
+                                           device=dev, out=out, pad=plan.pad[0]), dr, pixels=S[1][0] * S[1][1])
             if need_src:
-                src_grads = _input_grads(B, drv, co[0], wk, saved, S[0], need_src, dt, cache, dev)
+                src_grads = _input_grads(B, drv, co[0], wk, saved, S[0], need_src, dt, cache, dev, plan.pad[0])
             if need_w:
                 W.done([wk], lane)
             break
         j, cprev = k - 1, co[k - 1]
         if need_w:  # D = dr_k (grid S[k+1]), G = conv_k input = ad[k-1]
             out = W.dest(wk)
-            lane.run(lambda: ops.wgrad(B, 2, drv, co[k], L.nhwc_view(ad[j]), cprev, cprev, dt, device=dev, out=out), dr,
-                     pixels=S[k + 1][0] * S[k + 1][1])
+            lane.run(lambda: ops.wgrad(B, 2, drv, co[k], L.nhwc_view(ad[j]), cprev, cprev, dt, device=dev, out=out,
+                                       pad=plan.pad[k]), dr, pixels=S[k + 1][0] * S[k + 1][1])
         wd = ops.packed(cache, wk, L.PACK_CONV_DGRAD, cprev, co[k], dt)
         ga = _nhwc(B, 2 * S[k + 1][0], 2 * S[k + 1][1], cprev, dt, dev)
         _trace("G", ("ga", k), ga)
@@ -717,7 +752,8 @@ def gen_backward(plan, saved, gy, dt, cache, need_src, W):
         dr = _nhwc(B, *S[k], cprev, dt, dev)
         _conv_act_norm_backward(L.CONVT_S2, B, drv, co[k], wd, cprev, ga, L.nhwc_view(ga), dt, plan.bnd.get(j), mode,
                                 tab_d.get(j), st_d.get(j), L.nhwc_view(rd[j]), cprev, LRELU,
-                                L.nhwc_view(gcat[j], 0, *S[k]), 0.0, 0, L.nhwc_view(dr), None, [wk], W, lane, sync)
+                                L.nhwc_view(gcat[j], 0, *S[k]), 0.0, 0, L.nhwc_view(dr), None, [wk], W, lane, sync,
+                                plan.pad[k])
     if lane is not None:
         lane.join()
     return src_grads
@@ -741,6 +777,9 @@ class DiscPlan:
         self.sync, self.norm_names = _sync_kind(bns, {id(m): n for n, m in net.named_modules()})
         self.n = len(convs)
         self.strides = [c.stride[0] for c in convs]
+        names = {id(m): n for n, m in net.named_modules()}
+        self.conv_names = [names.get(id(c), "?") for c in convs]
+        self.pad = [_pad_of(c, n) for c, n in zip(convs, self.conv_names)]  # per conv: L.PAD_ZEROS / L.PAD_REFLECT
         self.in_c = convs[0].in_channels
         self.params = list(net.parameters())
 
@@ -794,10 +833,13 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
     xv = L.nhwc_view(xin)  # (of act[i], the input of conv_i)
     for i, cv in enumerate(plan.convs):
         s = plan.strides[i]
-        if s == 2:
+        if s == 2 and plan.pad[i] == L.PAD_ZEROS:  # (a reflect layer takes every extent >= 2, as torch: section 8i)
             assert dims[i][0] % 2 == 0 and dims[i][1] % 2 == 0, "stride-2 discriminator layers need even sizes"
         h, w = _conv_out(dims[i][0], s), _conv_out(dims[i][1], s)
         cout = cv.out_channels
+        pad = plan.pad[i]
+        if pad == L.PAD_REFLECT:
+            _check_reflect_plane(plan.conv_names[i], B, cv.in_channels, *dims[i])
         wp = ops.packed(cache, cv.weight, L.PACK_CONV_FWD, cout, chans[i], dt)
         kind = L.CONV_S2 if s == 2 else L.CONV_S1
         if i == n - 1:
@@ -805,7 +847,7 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
                 out = torch.empty((B, cout, 0, 0), dtype=torch.float32, device=dev)
                 break
             out = torch.empty((B, cout, h, w), dtype=torch.float32, device=dev)
-            ops.conv(kind, B, xv, chans[i], wp, cout, L.nchw_view(out), dt, bias=cv.bias, out_f32=True)
+            ops.conv(kind, B, xv, chans[i], wp, cout, L.nchw_view(out), dt, bias=cv.bias, out_f32=True, pad=pad)
             break
         tab, st = None, None
         a = _nhwc(B, h, w, cout, dt, dev)
@@ -816,15 +858,16 @@ def disc_forward(plan, sources, train, dt, cache, save, inputs=None, stats_only=
             ov = L.nhwc_view(o)
             # (stats_only: only the logits layer reads the last activation -- no pass)
             t, st = _conv_norm_act(kind, B, xv, chans[i], wp, cout, ov, dt, plan.bns[i - 1], mode, ov,
-                                   None if (stats_only and i == n - 2) else av, LRELU, None, 0.0, None, defer, save, sync)
+                                   None if (stats_only and i == n - 2) else av, LRELU, None, 0.0, None, defer, save, sync,
+                                   pad)
             if t is not None:
                 tab = (t[0], t[1])
-        elif ops.conv_act(kind, B, xv, chans[i], wp, cout, av, LRELU, dt, bias=cv.bias):
+        elif pad == L.PAD_ZEROS and ops.conv_act(kind, B, xv, chans[i], wp, cout, av, LRELU, dt, bias=cv.bias):
             o = a  # no raw output: the backward's LeakyReLU test sees the same signs in the activation
         else:
             o = _nhwc(B, h, w, cout, dt, dev)
             ov = L.nhwc_view(o)
-            ops.conv(kind, B, xv, chans[i], wp, cout, ov, dt, bias=cv.bias)
+            ops.conv(kind, B, xv, chans[i], wp, cout, ov, dt, bias=cv.bias, pad=pad)
             ops.bn_apply(B, ov, cout, dt, None, av, LRELU)
         xv = av
         raw.append(o)
@@ -866,6 +909,7 @@ def disc_backward(plan, saved, gout, dt, cache, need_src, W):
         cv = plan.convs[i]
         s = plan.strides[i]
         cout = cv.out_channels
+        pad = plan.pad[i]
         gv = L.nhwc_view(g, 0, h, w)  # gradient wrt conv_i output (pre-activation / pre-BN), gch channels
         _trace("D", ("g", i), g)
         if need_w:
@@ -878,19 +922,20 @@ def disc_backward(plan, saved, gout, dt, cache, need_src, W):
 
             def wg():  # (run at once, by lane.run)
                 if bc is not None:  # the constant-1 channel's tap (1,1) is the bias gradient (disc_forward)
-                    dW = ops.wgrad(B, s, gv, gch, L.nhwc_view(act[i]), chans[i], bc + 1, dt, device=dev, rows=cout)
+                    dW = ops.wgrad(B, s, gv, gch, L.nhwc_view(act[i]), chans[i], bc + 1, dt, device=dev, rows=cout,
+                                   pad=pad)
                     dw_out.copy_(dW[:cout, :saved["cin"]])
                     db_out.copy_(dW[:cout, bc, 1, 1])
                     return
                 ops.wgrad(B, s, gv, gch, L.nhwc_view(act[i]), chans[i], saved["cin"] if i == 0 else chans[i], dt,
-                          device=dev, rows=cout, out=dw_out)
+                          device=dev, rows=cout, out=dw_out, pad=pad)
                 if cv.bias is not None:
                     ops.chan_sum(B, gv, gch, cout, dt, dev, out=db_out)
             lane.run(wg, g, pixels=h * w)
         own = [cv.weight] + ([cv.bias] if cv.bias is not None else [])
         if i == 0:
             if need_src:
-                src_grads = _input_grads(B, gv, gch, cv.weight, saved, dims[0], need_src, dt, cache, dev)
+                src_grads = _input_grads(B, gv, gch, cv.weight, saved, dims[0], need_src, dt, cache, dev, pad)
             if need_w:
                 W.done(own, lane)
             break
@@ -909,7 +954,7 @@ def disc_backward(plan, saved, gout, dt, cache, need_src, W):
         _trace("D", ("ga", i), ga)
         _conv_act_norm_backward(dkind, B, gv, gch, wd, cin, ga, L.nhwc_view(ga), dt,
                                 plan.bns[i - 2] if i >= 2 else None, mode, tabs[i], stats[i], L.nhwc_view(raw[i]), cin,
-                                LRELU, None, 0.0, 0, L.nhwc_view(gn), None, own, W, lane, sync)
+                                LRELU, None, 0.0, 0, L.nhwc_view(gn), None, own, W, lane, sync, pad)
         g, gch, h, w = gn, cin, ph, pw
     if lane is not None:
         lane.join()

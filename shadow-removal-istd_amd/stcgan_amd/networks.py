@@ -24,8 +24,20 @@ concatenation without materialising it (what ``torch.cat(..., 1)`` would give).
 ``ConvTranspose2d(4, 2, 1)`` of the up path becomes ``nn.Upsample(scale_factor=2, mode="nearest")`` +
 ``nn.Conv2d(3, 1, 1)`` (resize-convolution, no checkerboard artifacts).  The same HIP kernels run it: with zero
 padding the pair is exactly a ConvTranspose2d whose 4x4 weight is a fixed sum of the 3x3 taps.
-``padding_mode`` is ``"zeros"``; the reference's helper uses ``"reflect"`` (equal to replicate padding of the
-low-resolution input by one pixel), which the zero-filling halo loaders cannot express: out of scope, refused.
+The up convs' ``padding_mode`` is ``"zeros"``; the reference's helper uses ``"reflect"`` there (equal to replicate
+padding of the low-resolution input by one pixel), which the ConvT kernels that run the pair cannot express: out of
+scope on the up path, refused.
+
+``padding_mode`` (``"zeros"``, the default, or ``"reflect"``; both factories): with ``"reflect"`` every
+``nn.Conv2d(kernel_size=4)`` of the tree -- the generator's down convs, all convs of the discriminator -- is built with
+``padding_mode="reflect"``, as the convs of the reference's src/models (mnet.py, patchgan.py, unet.py) are.  No
+state_dict key or shape changes; the network computes what torch computes for that tree.  ConvTranspose2d has no padding
+mode and keeps zeros, as do the 3x3 up convs of ``no_conv_t``.  The reflect layers run the reflect instantiations of
+the gather kernels and the unfused step forms.  A reflect conv over a plane one pixel high or
+wide raises RuntimeError as torch does; a generator input with an odd level (H or W no multiple of 2^(num_downs-1))
+raises NotImplementedError at call time, naming the level (the reference zero-pads such a level to even and reflects
+about the padded extent: not built).  The reflect discriminator follows torch for every extent >= 2, odd stride-2
+planes included.
 ``conv_t_state_dict()`` exports such a generator as the plain ST-CGAN one.
 
 ``activation`` (the ``--activation`` option of the same line, src/models/opt_layers.py:7-18): the generator's output head,
@@ -134,6 +146,16 @@ def get_activation(key):
     if key == "htanh":
         return nn.Hardtanh(min_val=-1.0, max_val=1.0, inplace=True)
     return None
+
+
+PADDING_MODES = ("zeros", "reflect")
+
+
+def check_padding_mode(v):
+    """A padding mode of the 4x4 convs as one of PADDING_MODES (ValueError otherwise)."""
+    if not isinstance(v, str) or v not in PADDING_MODES:
+        raise ValueError(f"stcgan_amd: padding_mode must be one of 'zeros', 'reflect', got {v!r}")
+    return v
 
 
 def check_flag(name, v):
@@ -258,8 +280,11 @@ class UnetGenerator(_HipNet):
     kind = "G"
 
     def __init__(self, in_channels, out_channels, ngf=64, num_downs=8, norm_layer=nn.BatchNorm2d,
-                 use_dropout=False, drop_rate=None, no_conv_t=False, activation="tanh"):
-        """activation (the reference's keyword, src/main.py:295-297, src/models/opt_layers.py:7-18): the module after the
+                 use_dropout=False, drop_rate=None, no_conv_t=False, activation="tanh", padding_mode="zeros"):
+        """padding_mode: "zeros" (default) or "reflect" -- the padding mode of the num_downs 4x4 down convs (module
+        docstring); the up layers keep zeros.  Read from the conv modules when the launch plan is
+        made.  Composes with every other option.
+        activation (the reference's keyword, src/main.py:295-297, src/models/opt_layers.py:7-18): the module after the
         outermost up layer -- "tanh" (default) nn.Tanh, "sigmoid" nn.Sigmoid, "htanh" nn.Hardtanh(-1, 1), "none" / None
         nothing (the outermost Sequential then has 4 modules).  None of them has parameters: every state_dict key is the
         default generator's and checkpoints load across heads.  The head runs in the output ConvT's epilogue and in the
@@ -268,8 +293,8 @@ class UnetGenerator(_HipNet):
         no_conv_t (the reference's keyword, src/models/opt_layers.py:39-56): each up layer is
         nn.Sequential(nn.Upsample(scale_factor=2, mode="nearest"), nn.Conv2d(cin, cout, 3, 1, 1)) at the ConvTranspose2d's
         index, its keys ``...model.N.1.weight`` [cout, cin, 3, 3] (and ``model.3.1.bias`` on the outermost layer).
-        padding_mode is "zeros": the reference helper's "reflect" (a replicate halo of the low-resolution input) is
-        out of scope, the halo loaders zero-fill.  Composes with every other option.
+        Their padding_mode is "zeros" whatever ``padding_mode`` says: the reference helper's "reflect" (a replicate
+        halo of the low-resolution input) is out of scope.  Composes with every other option.
         use_dropout: nn.Dropout after the up-norm of the num_downs - 5 blocks above the innermost one, as the
         reference (p = 0.5; ``drop_rate`` overrides it, 0 <= drop_rate < 1).  Train mode only; the masks are a
         counter-based function of this generator's {seed, offset} (set_dropout_seed / dropout_state).  p is read
@@ -281,21 +306,22 @@ class UnetGenerator(_HipNet):
         self._drop_state = None  # device int64 {seed, offset}: a plain attribute, the state_dict keys stay the reference's
         self.no_conv_t = nct = check_flag("no_conv_t", no_conv_t)
         self.activation = check_activation(activation)
+        self.padding_mode = pm = check_padding_mode(padding_mode)
         unet_block = UnetSkipConnectionBlock(ngf * 8, ngf * 8, input_nc=None, submodule=None,
-                                             norm_layer=norm_layer, innermost=True, no_conv_t=nct)
+                                             norm_layer=norm_layer, innermost=True, no_conv_t=nct, padding_mode=pm)
         for _ in range(num_downs - 5):
             unet_block = UnetSkipConnectionBlock(ngf * 8, ngf * 8, input_nc=None, submodule=unet_block,
                                                  norm_layer=norm_layer, use_dropout=bool(use_dropout), drop_rate=p,
-                                                 no_conv_t=nct)
+                                                 no_conv_t=nct, padding_mode=pm)
         unet_block = UnetSkipConnectionBlock(ngf * 4, ngf * 8, input_nc=None, submodule=unet_block,
-                                             norm_layer=norm_layer, no_conv_t=nct)
+                                             norm_layer=norm_layer, no_conv_t=nct, padding_mode=pm)
         unet_block = UnetSkipConnectionBlock(ngf * 2, ngf * 4, input_nc=None, submodule=unet_block,
-                                             norm_layer=norm_layer, no_conv_t=nct)
+                                             norm_layer=norm_layer, no_conv_t=nct, padding_mode=pm)
         unet_block = UnetSkipConnectionBlock(ngf, ngf * 2, input_nc=None, submodule=unet_block,
-                                             norm_layer=norm_layer, no_conv_t=nct)
+                                             norm_layer=norm_layer, no_conv_t=nct, padding_mode=pm)
         self.model = UnetSkipConnectionBlock(out_channels, ngf, input_nc=in_channels, submodule=unet_block,
                                              outermost=True, norm_layer=norm_layer, no_conv_t=nct,
-                                             activation=self.activation)
+                                             activation=self.activation, padding_mode=pm)
 
     def conv_t_state_dict(self):
         """The state_dict of the equivalent plain ST-CGAN generator (ConvTranspose2d up layers): each up layer's
@@ -378,14 +404,16 @@ class UnetSkipConnectionBlock(nn.Module):
     Executed only as part of UnetGenerator (the whole U-Net is one fused HIP schedule)."""
 
     def __init__(self, outer_nc, inner_nc, input_nc=None, submodule=None, outermost=False, innermost=False,
-                 norm_layer=nn.BatchNorm2d, use_dropout=False, drop_rate=0.5, no_conv_t=False, activation="tanh"):
+                 norm_layer=nn.BatchNorm2d, use_dropout=False, drop_rate=0.5, no_conv_t=False, activation="tanh",
+                 padding_mode="zeros"):
         super().__init__()
         self.outermost = outermost
         self.innermost = innermost
         use_bias = isinstance(norm_layer, nn.InstanceNorm2d)  # always False, as in the reference
         if input_nc is None:
             input_nc = outer_nc
-        downconv = nn.Conv2d(input_nc, inner_nc, kernel_size=4, stride=2, padding=1, bias=use_bias)
+        downconv = nn.Conv2d(input_nc, inner_nc, kernel_size=4, stride=2, padding=1, bias=use_bias,
+                             padding_mode=check_padding_mode(padding_mode))
         downrelu = nn.LeakyReLU(0.2, True)
         downnorm = norm_layer(inner_nc)
         uprelu = nn.ReLU(True)
@@ -420,28 +448,33 @@ class NLayerDiscriminator(_HipNet):
 
     kind = "D"
 
-    def __init__(self, in_channels, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, use_sigmoid=False):
+    def __init__(self, in_channels, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, use_sigmoid=False,
+                 padding_mode="zeros"):
+        """padding_mode: "zeros" (default) or "reflect" -- the padding mode of all n_layers + 2 convs (module docstring;
+        DESIGN.md section 8i)."""
         super().__init__()
+        self.padding_mode = pm = check_padding_mode(padding_mode)
         self.norm_kind = check_norm_layer(norm_layer)
         if use_sigmoid:
             raise NotImplementedError("stcgan_amd: use_sigmoid=True is not on the ST-CGAN path "
                                       "(STCGAN/stcgan.py:39,41)")
         use_bias = isinstance(norm_layer, nn.InstanceNorm2d)
         kw, padw = 4, 1
-        sequence = [nn.Conv2d(in_channels, ndf, kernel_size=kw, stride=2, padding=padw), nn.LeakyReLU(0.2, True)]
+        sequence = [nn.Conv2d(in_channels, ndf, kernel_size=kw, stride=2, padding=padw, padding_mode=pm),
+                    nn.LeakyReLU(0.2, True)]
         nf_mult = 1
         for n in range(1, n_layers):
             nf_mult_prev = nf_mult
             nf_mult = min(2 ** n, 8)
             sequence += [nn.Conv2d(ndf * nf_mult_prev, ndf * nf_mult, kernel_size=kw, stride=2, padding=padw,
-                                   bias=use_bias),
+                                   bias=use_bias, padding_mode=pm),
                          norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True)]
         nf_mult_prev = nf_mult
         nf_mult = min(2 ** n_layers, 8)
         sequence += [nn.Conv2d(ndf * nf_mult_prev, ndf * nf_mult, kernel_size=kw, stride=1, padding=padw,
-                               bias=use_bias),
+                               bias=use_bias, padding_mode=pm),
                      norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True)]
-        sequence += [nn.Conv2d(ndf * nf_mult, 1, kernel_size=kw, stride=1, padding=padw)]
+        sequence += [nn.Conv2d(ndf * nf_mult, 1, kernel_size=kw, stride=1, padding=padw, padding_mode=pm)]
         self.model = nn.Sequential(*sequence)
 
     def _make_plan(self):

@@ -93,12 +93,70 @@ def plan_of(kind, B, gh, gw, cin, cout, dt):
     return tuple(out)
 
 
+_DGRAD_OF = {L.CONVT_S2: L.CONV_S2, L.CONV_S1_DGRAD: L.CONV_S1}  # the Conv2d kind an input-gradient kind belongs to
+
+
+def conv_pad_query(kind, B, H, W, cin, cout, dt, pad, out_f32=False, force=None):
+    """(workspace bytes, stats chunks, plan) of stc_conv_pad_fwd for a Conv2d kind over an H x W input."""
+    key = ("cpq", kind, B, H, W, cin, cout, dt, pad, bool(out_f32), None if force is None else tuple(force))
+    r = _MEMO.get(key)
+    if r is None:
+        ws, nch, po = ctypes.c_int64(), ctypes.c_int32(), (ctypes.c_int32 * 5)()
+        fp = (ctypes.c_int32 * 2)(*force) if force is not None else None
+        check(lib().stc_conv_pad_fwd_query(L.dtype_code(dt), kind, pad, B, H, W, cin, cout, int(out_f32), fp,
+                                           ctypes.byref(ws), ctypes.byref(nch), po), "stc_conv_pad_fwd_query")
+        r = _MEMO[key] = (ws.value, nch.value, tuple(po))
+    return r
+
+
+def conv_pad_dgrad_query(kind, B, H, W, cout, cin, dt, pad, out_f32=False):
+    """(workspace bytes, plan) of stc_conv_pad_dgrad: the input gradient (cin channels, H x W) of a Conv2d kind; under
+    reflect the plan is the frame conv's and the workspace holds the fp32 frame and its split-K slabs."""
+    key = ("cpdq", kind, B, H, W, cout, cin, dt, pad, bool(out_f32))
+    r = _MEMO.get(key)
+    if r is None:
+        ws, po = ctypes.c_int64(), (ctypes.c_int32 * 5)()
+        check(lib().stc_conv_pad_dgrad_query(L.dtype_code(dt), kind, pad, B, H, W, cout, cin, int(out_f32),
+                                             ctypes.byref(ws), po), "stc_conv_pad_dgrad_query")
+        r = _MEMO[key] = (ws.value, tuple(po))
+    return r
+
+
+def conv_pad(kind, B, xv, cin, w_packed, cout, yv, dt, pad, bias=None, act=None, out_f32=False, stats=False):
+    """A Conv2d k4 p1 with a padding mode, ``kind`` as conv() takes it: a Conv2d kind is the forward
+    (stc_conv_pad_fwd), STC_CONVT_S2 / STC_CONV_S1_DGRAD the input gradient of the stride-2 / stride-1 conv
+    (stc_conv_pad_dgrad: xv the output gradient, yv the input gradient).  stats (forward): returns the BatchNorm
+    partials (part, chunks) of the stored output.  DESIGN.md section 8i."""
+    dev = w_packed.device
+    code = L.dtype_code(dt)
+    if kind in _DGRAD_OF:
+        assert bias is None and act is None and not stats
+        nbytes, _ = conv_pad_dgrad_query(_DGRAD_OF[kind], B, yv.H, yv.W, cin, cout, dt, pad, out_f32)
+        ws, nb = _ws(nbytes, dev)
+        check(lib().stc_conv_pad_dgrad(code, _DGRAD_OF[kind], pad, B, xv, cin, ptr(w_packed), cout, yv, int(out_f32),
+                                       ptr(ws), nb, stream()), "stc_conv_pad_dgrad")
+        return None
+    nbytes, nch, _ = conv_pad_query(kind, B, xv.H, xv.W, cin, cout, dt, pad, out_f32)
+    ws, nb = _ws(nbytes, dev)
+    part = torch.empty((nch, cout, 4), dtype=torch.float32, device=dev) if stats else None
+    check(lib().stc_conv_pad_fwd(code, kind, pad, B, xv, cin, ptr(w_packed), cout, yv, ptr(bias), L.head_code(act),
+                                 int(out_f32), ptr(part), nch if stats else 0, None, ptr(ws), nb, stream()),
+          "stc_conv_pad_fwd")
+    return (part, nch) if stats else None
+
+
 def conv(kind, B, xv, cin, w_packed, cout, yv, dt, pro=None, slope=None, bias=None, tanh=False, out_f32=False,
-         force=None, act=None):
+         force=None, act=None, pad=L.PAD_ZEROS):
     """Implicit-GEMM conv family (stc_conv_fwd; force: a forced narrow-N tile through stc_conv_fwd_ex, tests).
-    act: the output head of the epilogue (_lib.head_code); tanh=True means act="tanh"."""
+    act: the output head of the epilogue (_lib.head_code); tanh=True means act="tanh".
+    pad: L.PAD_REFLECT runs conv_pad (no prologue, no forced plan); L.PAD_ZEROS is this function as ever."""
     if act is not None and tanh and L.head_code(act) != L.HEAD_TANH:
         raise ValueError(f"stcgan_amd: conv(tanh=True) together with act={act!r}")
+    if pad != L.PAD_ZEROS:
+        if pro is not None or slope is not None or force is not None:
+            raise ValueError("stcgan_amd: a reflect conv takes no prologue and no forced plan")
+        return conv_pad(kind, B, xv, cin, w_packed, cout, yv, dt, pad, bias=bias,
+                        act=act if act is not None else ("tanh" if tanh else None), out_f32=out_f32)
     tanh = L.head_code(act) if act is not None else int(bool(tanh))
     dev = w_packed.device
     if kind == L.CONVT_S2:
@@ -219,9 +277,12 @@ def conv_act_backward(kind, B, xv, cin, w_packed, cout, yv, dt, act_x, s_self, g
     return True
 
 
-def conv_stats(kind, B, xv, cin, w_packed, cout, yv, dt, bias=None, force=None):
+def conv_stats(kind, B, xv, cin, w_packed, cout, yv, dt, bias=None, force=None, pad=L.PAD_ZEROS):
     """Conv forward + fused BatchNorm partial statistics of its output (stc_conv_fwd_ex).
-    Returns (part [chunks, cout, 4] fp32, chunks) for bn_finalize."""
+    Returns (part [chunks, cout, 4] fp32, chunks) for bn_finalize.  pad=L.PAD_REFLECT: the reflect conv, the
+    partials from a pass over its stored output (conv_pad)."""
+    if pad != L.PAD_ZEROS:
+        return conv_pad(kind, B, xv, cin, w_packed, cout, yv, dt, pad, bias=bias, stats=True)
     dev = w_packed.device
     gh, gw = (xv.H, xv.W) if kind == L.CONVT_S2 else (yv.H, yv.W)
     if force is None and FORCE_CONV:
@@ -244,19 +305,20 @@ def conv_stats(kind, B, xv, cin, w_packed, cout, yv, dt, bias=None, force=None):
 
 
 def conv_bn_act(kind, B, xv, cin, w_packed, cout, yv, dt, bn, apply_x, y1, s1, y2=None, s2=0.0, defer=None,
-                drop=None):
+                drop=None, pad=L.PAD_ZEROS):
     """A BatchNorm layer's train-mode forward: conv into ``yv`` with the batch statistics, the BN finalize (running
     statistics updated) and the activation pass of ``apply_x`` into y1 [and y2] (y1 None: no pass) -- one library call
     (stc_conv_bn_fwd; the instrumented / forced-plan runs take the three separate calls).  Returns ((2, cout) scale /
     shift table, (mean, rstd)), views of one fp32 buffer.  defer (a list): the running statistics are left alone and
     (partials, chunks, cout, bn) is appended for bn_running_update.  drop (a dropout level, see dropout_next): the
-    activation pass applies the dropout mask (stc_conv_bn_fwd_drop, the same launches)."""
+    activation pass applies the dropout mask (stc_conv_bn_fwd_drop, the same launches).  pad=L.PAD_REFLECT: the
+    three separate calls, around the reflect conv."""
     dev = w_packed.device
     gh, gw = (xv.H, xv.W) if kind == L.CONVT_S2 else (yv.H, yv.W)
     upd = defer is None
-    if _timer is not None or (FORCE_CONV and (kind, B, gh, gw, cin, cout) in FORCE_CONV):
+    if pad != L.PAD_ZEROS or _timer is not None or (FORCE_CONV and (kind, B, gh, gw, cin, cout) in FORCE_CONV):
         t = torch.empty((2, cout), dtype=torch.float32, device=dev)
-        part, nch = conv_stats(kind, B, xv, cin, w_packed, cout, yv, dt)
+        part, nch = conv_stats(kind, B, xv, cin, w_packed, cout, yv, dt, pad=pad)
         st = bn_finalize_part(part, nch, cout, bn, t[0], t[1], update_running=upd)
         if not upd:
             defer.append((part, nch, cout, bn))
@@ -539,13 +601,42 @@ def _out_w(t, R, Cg_out, device):
     return t
 
 
+def wgrad_pad_query(stride, B, Hd, Wd, R, Cg, dt, pad, force=None):
+    """(workspace bytes, plan (cfg, BM, BN, splits, slab)) of stc_conv_pad_wgrad over the output grid Hd x Wd."""
+    key = ("wpq", stride, B, Hd, Wd, R, Cg, dt, pad, None if force is None else tuple(force))
+    r = _MEMO.get(key)
+    if r is None:
+        ws, po = ctypes.c_int64(), (ctypes.c_int32 * 5)()
+        fp = (ctypes.c_int32 * 2)(*force) if force is not None else None
+        check(lib().stc_conv_pad_wgrad_query(L.dtype_code(dt), L.CONV_S2 if stride == 2 else L.CONV_S1, pad, B, Hd, Wd,
+                                             R, Cg, fp, ctypes.byref(ws), po), "stc_conv_pad_wgrad_query")
+        r = _MEMO[key] = (ws.value, tuple(po))
+    return r
+
+
 def wgrad(B, stride, Dv, R, Gv, Cg, Cg_out, dt, dpro=None, dslope=None, gpro=None, gslope=None, device=None,
-          force=None, rows=None, rows_kernel=None, out=None):
+          force=None, rows=None, rows_kernel=None, out=None, pad=L.PAD_ZEROS):
     """Weight gradient [R][Cg_out][4][4] fp32 (stc_conv_wgrad_ex; force = optional {tile config, splits}),
     written into ``out`` when given (e.g. a view of a flat gradient buffer).
     rows: the number of nonzero (real) channels of D when the rest is padding -- a stride-1 layer with
-    1-2 of them goes to stc_conv_wgrad_rows (which then writes only R = ``rows`` rows when R == rows)."""
+    1-2 of them goes to stc_conv_wgrad_rows (which then writes only R = ``rows`` rows when R == rows).
+    pad=L.PAD_REFLECT (a Conv2d's weight gradient: Dv its output gradient, Gv its input): stc_conv_pad_wgrad, the
+    register-staged kernel with the reflect gather; no prologue, no rows kernel."""
     l = lib()
+    if pad != L.PAD_ZEROS:
+        if dpro is not None or gpro is not None or dslope is not None or gslope is not None:
+            raise ValueError("stcgan_amd: a reflect weight gradient takes no prologue")
+        if out is not None and out.shape[0] != R:  # real rows of a padded R: through a scratch
+            full = wgrad(B, stride, Dv, R, Gv, Cg, Cg_out, dt, device=device, force=force, pad=pad)
+            out.copy_(full[:out.shape[0]])
+            return out
+        nbytes, _ = wgrad_pad_query(stride, B, Dv.H, Dv.W, R, Cg, dt, pad, force)
+        ws, nb = _ws(nbytes, device)
+        dW = _out_w(out, R, Cg_out, device)
+        fp = (ctypes.c_int32 * 2)(*force) if force is not None else None
+        check(l.stc_conv_pad_wgrad(L.dtype_code(dt), L.CONV_S2 if stride == 2 else L.CONV_S1, pad, B, Dv, R, Gv, Cg,
+                                   Cg_out, ptr(dW), fp, ptr(ws), nb, stream()), "stc_conv_pad_wgrad")
+        return dW
     if (rows is not None and rows <= 2 and stride == 1 and (_ROWS_DEFAULT if rows_kernel is None else rows_kernel) and dpro is None and gpro is None and dslope is None
             and gslope is None and force is None and Cg % 64 == 0 and ((Dv.H + 4) * (Dv.W + 4) + 16384) * rows <= 40000):
         nbytes = l.stc_conv_wgrad_rows_workspace(B, Gv.H, rows, Cg)
@@ -855,13 +946,13 @@ def bn_bwd_apply_sync(B, xv, C, dt, dxv, g1, s1, g2, s2, bn_state, recs, count, 
 
 
 def conv_bn_act_sync(kind, B, xv, cin, w_packed, cout, yv, dt, bn, apply_x, y1, s1, y2=None, s2=0.0, defer=None,
-                     drop=None, gather=None):
+                     drop=None, gather=None, pad=L.PAD_ZEROS):
     """conv_bn_act on the statistics of all ranks: conv with its partials, pack, gather, the finalize over the ranks'
     records (every rank updates its running statistics with the global, unbiased-by-the-global-count values) and the
     activation pass.  defer (a list): (gathered records, world, cout, bn) is appended for bn_running_update."""
     upd = defer is None
     t = torch.empty((2, cout), dtype=torch.float32, device=w_packed.device)
-    part, nch = conv_stats(kind, B, xv, cin, w_packed, cout, yv, dt)
+    part, nch = conv_stats(kind, B, xv, cin, w_packed, cout, yv, dt, pad=pad)
     recs = gather(bn_stats_pack(part, nch, cout))
     st = bn_finalize_part(recs, recs.shape[0], cout, bn, t[0], t[1], update_running=upd)
     if not upd:

@@ -170,6 +170,13 @@ def check_activation(v):
     return networks.check_activation(v)
 
 
+def check_padding_mode(v):
+    """args.padding_mode: "zeros" or "reflect" (ValueError otherwise)."""
+    if not isinstance(v, str):
+        raise ValueError("stcgan_amd: args.padding_mode must be 'zeros' or 'reflect', got " + repr(v))
+    return networks.check_padding_mode(v)
+
+
 def check_nn_upconv(v):
     """args.NN_upconv as a bool (True / False / 0 / 1; ValueError otherwise)."""
     return networks.check_flag("args.NN_upconv", v)
@@ -218,10 +225,15 @@ class STCGAN(object):
         # "sigmoid" or "none" the caller's targets decide what that range means.
         self.activation = check_activation(getattr(args, "activation", "tanh"))
         up["activation"] = self.activation
+        # args.padding_mode ("zeros"): the padding mode of every 4x4 conv of all four networks, "zeros" or "reflect"
+        # (networks, padding_mode).  The keyword is passed only when it is not the default.
+        self.padding_mode = check_padding_mode(getattr(args, "padding_mode", "zeros"))
+        pm = dict(padding_mode=self.padding_mode) if self.padding_mode != "zeros" else {}
+        up.update(pm)
         self.G1 = networks.get_generator(in_channels=3, out_channels=1, ngf=ngf, **nl, **drop, **up)
         self.G2 = networks.get_generator(in_channels=3 + 1, out_channels=3, ngf=ngf, **nl, **drop, **up)
-        self.D1 = networks.get_discriminator(in_channels=3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False, **nl)
-        self.D2 = networks.get_discriminator(in_channels=3 + 3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False, **nl)
+        self.D1 = networks.get_discriminator(in_channels=3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False, **nl, **pm)
+        self.D2 = networks.get_discriminator(in_channels=3 + 3 + 1, ndf=ngf, n_layers=3, use_sigmoid=False, **nl, **pm)
         tasks = getattr(args, "tasks", ["train"])
         if "infer" in tasks and "train" not in tasks:
             assert args.load_weights_g1 is not None

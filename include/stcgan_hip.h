@@ -235,7 +235,10 @@ int64_t stc_conv_wgrad_workspace(int dtype, int B, int Hd, int Wd, int R, int Cg
  * splits (0 = auto)} for the bf16 LDS-DMA kernel, NULL = automatic.  No global state.
  * stc_conv_wgrad_query: workspace bytes and plan_out[5] = {tile config (-1: fp32 / prologue kernel),
  * BM, BN, pixel splits, slab (1: fp32 split slabs + the fixed-order transposing reduction)} for the
- * same arguments (bf16 assumes the LDS-DMA kernel's eligibility: aligned NHWC views, no prologue). */
+ * same arguments.  The query takes a D grid and no stride or views: it answers for dense NHWC views, reports the
+ * plan of the stride-2 call with G on the doubled grid (on a 31-wide D grid of odd height, which only the stride-1
+ * halo tile plans for, the stride-1 plan) and a workspace that is enough for either stride, with or without a
+ * prologue.  stc_conv_wgrad_route (below) answers for one call's actual views and stride. */
 int stc_conv_wgrad_ex(int dtype, int B, int stride,
                       stc_view D, int R,
                       const float* d_scale, const float* d_shift, int d_act, float d_slope,
@@ -302,6 +305,22 @@ int stc_conv_pad_wgrad_query(int dtype, int kind, int pad_mode, int B, int Hd, i
 int stc_conv_wgrad_rows(int dtype, int B, stc_view D, int R, int R_out, stc_view G, int Cg, int Cg_out,
                         float* dW, void* workspace, int64_t workspace_bytes, void* stream);
 int64_t stc_conv_wgrad_rows_workspace(int B, int IH, int R_out, int Cg);
+
+/* The route of one weight-gradient call, for its actual views and stride (the queries above take
+ * a D grid only and answer for dense views and either stride).  rows: the real channels of D when the rest is channel
+ * padding (0: not asked); prologue: non-zero when the call has a d/g scale or activation; pad_mode: STC_PAD_*.
+ *   workspace_bytes  what the call named below needs
+ *   plan_out[5]      {tile config (-1: none), BM, BN, slabs, slab} as stc_conv_wgrad_query reports it
+ *   kernel_out[2]    {kernel, reduce}: kernel 0 none (no pixels), 1 the register-staged tile (wgrad_kernel /
+ *                    wgrad_reflect_kernel), 2 the bf16 LDS-DMA tile, 3 the same with loader waves, 4 the halo tile,
+ *                    5 the rows kernel, 6 the MFMA rows kernel; reduce 0 none, 1 wgrad_reduce_kernel, 2 _v4, 3 _many
+ *   name_out         the kernel's name as a profiler prints it (at most name_cap bytes, NUL-terminated)
+ * Kernels 5 and 6 are launched by stc_conv_wgrad_rows, a reflect call by stc_conv_pad_wgrad, every other by
+ * stc_conv_wgrad_ex.  Any output pointer may be NULL.  As stc_conv_pad_wgrad, it refuses a force_plan under
+ * STC_PAD_REFLECT. */
+int stc_conv_wgrad_route(int dtype, int B, int stride, stc_view D, int R, int rows, stc_view G, int Cg, int Cg_out,
+                         int prologue, int pad_mode, const int32_t* force_plan, int64_t* workspace_bytes,
+                         int32_t* plan_out, int32_t* kernel_out, char* name_out, int name_cap);
 
 /* ---- weight packing ----------------------------------------------------------
  * W is a torch weight [P][Q][4][4] fp32.  out is [phases][N_pad][T][C_pad] of dtype.

@@ -1,6 +1,7 @@
-// Host-side interface between the conv files: the one function that decides which kernel a conv call runs
-// (conv_route, conv_route.cpp; the table is DESIGN.md section 4), and every function one .hip file calls in another,
-// declared once -- the defining file includes this header, so the compiler checks each signature.
+// Host-side interface between the conv files: the two functions that decide which kernel a call runs -- conv_route
+// (conv_route.cpp) for the forward and input-gradient convs, wgrad_route (wgrad_route.cpp) for the weight gradient; the
+// tables are DESIGN.md section 4 -- and every function one .hip file calls in another, declared once: the defining
+// file includes this header, so the compiler checks each signature.
 #pragma once
 #include "common.hpp"
 
@@ -129,12 +130,77 @@ int bf16_narrow_fwd(int kind, int B, stc_view x, int Cin, const void* w_packed, 
                     const float* bias, int epi_tanh, int out_f32, void* ws, int64_t ws_bytes, hipStream_t st,
                     const int32_t* force);
 
-// ---- wgrad.hip / wgrad_bf16.hip
-void wgrad_reduce_launch(const float* ws, int nsplit, int R, int Cg, int Cg_out, float* dW, hipStream_t st);
+// ---- the weight gradient's route (wgrad_route, wgrad_route.cpp; the table is DESIGN.md section 4)
+struct WgPlan {  // wgrad.hip: the register-staged wgrad_kernel / wgrad_reflect_kernel
+  int BM, BN, mtiles, ntiles, nsplit, pchunk;
+};
+struct WbPlan {  // wgrad_bf16.hip: the LDS-DMA tiles and the halo tile
+  int cfg, BM, BN, mtiles, ntiles, nsplit, pchunk;
+  bool slab;    // partial sums go to fp32 slabs + the ordered reduce (always when nsplit > 1)
+  bool cmajor;  // channel-group-major columns (WbParams::cmajor): one split whose tiles store torch layout directly
+  bool s1v;     // planned over the stride-1 halo tile's virtual grid (GH + 1) x (GW + 1)
+};
+
+struct WgradAsk {  // everything the choice of kernel depends on
+  int dtype, B, stride;
+  stc_view D, G;
+  int R, Cg, Cg_out;
+  int rows;          // real channels of D when the rest is padding; 0: not asked / the rows kernels off
+  bool rows_direct;  // stc_conv_wgrad_rows called directly: its own checks decide, not the automatic LDS budget
+  bool prologue;     // any of d / g scale, shift, activation
+  int pad;           // STC_PAD_ZEROS / STC_PAD_REFLECT
+  const int32_t* force;  // force_plan {tile config, pixel splits}
+};
+
+enum WgradKernel { WG_NONE, WG_FP_TILE, WG_BF16_TILE, WG_BF16_LD, WG_HALO, WG_ROWS, WG_ROWS_MFMA };
+enum WgradReduce { WR_NONE, WR_PLAIN, WR_V4, WR_MANY };
+
+struct WgradRoute {
+  WgradKernel kernel;  // WG_NONE: no pixels (B * D.H * D.W == 0), nothing to launch
+  WgradReduce reduce;  // WR_NONE: the kernel writes dW itself
+  int64_t ws_bytes;
+  int32_t plan[5];  // {tile config (-1: none), BM, BN, slabs, slab} as stc_conv_wgrad_query reports it
+  // what the launchers need and do not derive again
+  int slabs;  // fp32 slabs the reduce sums (0: none)
+  WgPlan fp;  // WG_FP_TILE
+  WbPlan wb;  // WG_BF16_TILE, WG_BF16_LD, WG_HALO
+  int pmode, lg_gw, lg_ghw;  // WbParams' pixel mapping
+  int GH, GW;                // the reduction grid: D's, or the stride-1 halo tile's virtual grid
+  int halo_tc;               // WG_HALO: grid columns per tile row (8 .. 64)
+  bool halo_s1;              // WG_HALO: the stride-1 form
+  int rows_parts;            // WG_ROWS / WG_ROWS_MFMA: slabs per image
+  size_t lds;                // dynamic LDS bytes of the launch
+  char name[96];             // the kernel as a profiler prints it (the timer label)
+};
+
+WgradRoute wgrad_route(const WgradAsk& a);
+
+// bytes of nsplit fp32 slabs [R][16 Cg]
+static inline int64_t wgrad_slab_bytes(int nsplit, int R, int Cg) { return (int64_t)nsplit * R * 16LL * Cg * 4; }
+
+// a dense NHWC view of a shape-only query: no pointer, batch stride 0
+static inline stc_view dense_view(int H, int W, int C) {
+  stc_view v{};
+  v.H = H; v.W = W; v.rs = (int64_t)W * C; v.ps = C; v.cs = 1;
+  return v;
+}
+
+// ---- wgrad.hip
+WgPlan wg_plan(int P, int R, int Cg);
+WgradReduce wgrad_reduce_kind(int nsplit, int R, int Cg, int Cg_out);
+void wgrad_reduce_launch(WgradReduce kind, const float* ws, int nsplit, int R, int Cg, int Cg_out, float* dW,
+                         hipStream_t st);
+// which rows kernel takes the ask by the kernels' own conditions (WG_NONE: neither); fills rows_parts, lds
+WgradKernel wgrad_rows_kind(const WgradAsk& a, WgradRoute& r);
+
+// ---- wgrad_bf16.hip
 bool wgrad_bf16_eligible(int B, const stc_view& D, int R, const stc_view& G, int Cg);
-int64_t wgrad_bf16_workspace(int B, int Hd, int Wd, int R, int Cg, const int32_t* force);
-void wgrad_bf16_plan(int B, int Hd, int Wd, int R, int Cg, const int32_t* force, int32_t* plan_out);
-int wgrad_bf16(int B, int stride, stc_view D, int R, stc_view G, int Cg, int Cg_out, float* dW, void* workspace,
-               int64_t workspace_bytes, hipStream_t st, const int32_t* force);
+// g_on_grid: G is exactly the doubled grid (stride 2) / the grid + 1 (stride 1), which the halo tile needs
+WbPlan wb_plan(int B, int GH, int GW, int stride, bool g_on_grid, int R, int Cg, const int32_t* force);
+// the launch of plan r.wb on the D grid GH x GW: kernel, pixel mapping, reduction grid, LDS bytes, name
+void wb_launch_shape(int GH, int GW, WgradRoute& r);
+// launches r.kernel, one of WG_BF16_TILE, WG_BF16_LD, WG_HALO
+int wgrad_bf16(const WgradAsk& a, const WgradRoute& r, float* dW, void* workspace, int64_t workspace_bytes,
+               hipStream_t st);
 
 }  // namespace stc

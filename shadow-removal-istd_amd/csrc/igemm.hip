@@ -454,11 +454,6 @@ static ConvAsk conv_ask(int dtype, int kind, int B, const stc_view& x, int Cin, 
 // the GEMM grid Hg x Wg, channel offset 0, 16-byte aligned base, no second gradient -- and batch stride 0: a shape
 // has no allocation, so the limits the kernels put on a view's size in memory (2 GiB of input, 2^31 output elements,
 // both growing with B * bs) count as met.  The _ex forms and the launches answer for the real views.
-static stc_view dense_view(int H, int W, int C) {
-  stc_view v{};
-  v.H = H; v.W = W; v.rs = (int64_t)W * C; v.ps = C; v.cs = 1;
-  return v;
-}
 static ConvAsk shape_ask(int dtype, int kind, int B, int Hg, int Wg, int Cin, int Cout) {
   const int d = kind == STC_CONV_S1 ? 1 : (kind == STC_CONV_S1_DGRAD ? -1 : 0);  // conv s1: 31 x 31 from 32 x 32
   const stc_view grid = dense_view(Hg, Wg, kind == STC_CONVT_S2 ? Cin : Cout);

@@ -156,36 +156,6 @@ int64_t wgrad_reduce_blocks(int R, int Cg_out) {
   return std::min<long long>((total + 127) / 128, 16384);
 }
 
-// The same sum for small outputs over many slabs (the 3-8 channel first/last layers: P = B*256*256
-// pixels split up to 256 ways, R*Cg_out*4 < 8192 output units): one wave per (r, ci, 4 taps) unit,
-// lane l summing slabs l, l + 64, ... in order, then a fixed xor-butterfly across the lanes
-// (deterministic; a thread per unit walking 256 slabs serially was latency-bound at 40-70 us).
-__global__ void __launch_bounds__(256) wgrad_reduce_wide_kernel(const float* __restrict__ ws, int nsplit, int R, int Cg,
-                                                                int Cg_out, float* __restrict__ dW) {
-  const int lane = threadIdx.x & 63;
-  const long long unit = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const long long total = (long long)R * Cg_out * 4;
-  if (unit >= total) return;
-  const int g = (int)(unit & 3);
-  const long long rc = unit >> 2;
-  const int ci = (int)(rc % Cg_out);
-  const int r = (int)(rc / Cg_out);
-  const long long Ncol = 16LL * Cg;
-  const long long slab = (long long)R * Ncol;
-  const float* src = ws + (long long)r * Ncol + (long long)(4 * g) * Cg + ci;
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int sp = lane; sp < nsplit; sp += 64) {
-    const float* a = src + (long long)sp * slab;
-    acc.x += a[0]; acc.y += a[Cg]; acc.z += a[2 * Cg]; acc.w += a[3 * Cg];
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    acc.x += __shfl_xor(acc.x, o, 64); acc.y += __shfl_xor(acc.y, o, 64);
-    acc.z += __shfl_xor(acc.z, o, 64); acc.w += __shfl_xor(acc.w, o, 64);
-  }
-  if (lane == 0) *reinterpret_cast<float4*>(dW + ((long long)r * Cg_out + ci) * 16 + 4 * g) = acc;
-}
-
 // The same fixed-order sum with more bytes in flight (the kernel above keeps 8 four-byte loads per
 // thread outstanding and was latency-bound at ~17 us for 64 slabs of 512 KB): a block = one row r x
 // 64 channels x 16 taps, a thread = (tap, 4 channels) reading one 16-byte vector per slab, 8 slabs
@@ -233,7 +203,7 @@ __global__ void __launch_bounds__(256) wgrad_reduce_v4_kernel(const float* __res
 // The same sum for small outputs over many slabs (the first layers' 256 splits of a 64|128 x 128 dW, the logits
 // layer's 64 image parts): a block = one row r x 64 slab columns, thread = (float4 column cq, slab lane sl < 16): lane
 // sl sums slabs sl, sl + 16, ... in order with 8 loads in flight, then the 16 lanes' partials are added in lane order
-// through LDS; the wave-per-unit kernel above kept only 4 scalar loads per lane in flight (11-20 us for 256 slabs; this
+// through LDS; a wave per (r, ci, 4 taps) unit kept only 4 scalar loads per lane in flight (11-20 us for 256 slabs; this
 // one 5-6 us, a 512-thread variant with 32 slab lanes no faster).
 __global__ void __launch_bounds__(256) wgrad_reduce_many_kernel(const float* __restrict__ ws, int nsplit, int R, int Cg,
                                                                 int Cg_out, float* __restrict__ dW) {
@@ -278,17 +248,23 @@ __global__ void __launch_bounds__(256) wgrad_reduce_many_kernel(const float* __r
   }
 }
 
-void wgrad_reduce_launch(const float* ws, int nsplit, int R, int Cg, int Cg_out, float* dW, hipStream_t st) {
+// Which of the three sums the slabs (every entry point requires Cg % 4 == 0, which the two vector kernels need)
+WgradReduce wgrad_reduce_kind(int nsplit, int R, int Cg, int Cg_out) {
   const long long units = (long long)R * Cg_out * 4;
-  if (Cg % 4 == 0 && Cg_out >= 64 && !(units < 8192 && nsplit >= 16))
+  const bool many = units < 8192 && nsplit >= 16;  // a small output over many slabs
+  if (Cg % 4 != 0) return WR_PLAIN;
+  if (many) return WR_MANY;
+  return Cg_out >= 64 ? WR_V4 : WR_PLAIN;
+}
+
+void wgrad_reduce_launch(WgradReduce kind, const float* ws, int nsplit, int R, int Cg, int Cg_out, float* dW,
+                         hipStream_t st) {
+  if (kind == WR_V4)
     hipLaunchKernelGGL(wgrad_reduce_v4_kernel, dim3((unsigned)(R * ((Cg_out + 63) / 64))), dim3(256), 0, st, ws, nsplit,
                        R, Cg, Cg_out, dW);
-  else if (units < 8192 && nsplit >= 16 && Cg % 4 == 0)
+  else if (kind == WR_MANY)
     hipLaunchKernelGGL(wgrad_reduce_many_kernel, dim3((unsigned)(R * ((16LL * Cg + 63) / 64))), dim3(256), 0, st, ws,
                        nsplit, R, Cg, Cg_out, dW);
-  else if (units < 8192 && nsplit >= 16)
-    hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, st, ws, nsplit, R, Cg,
-                       Cg_out, dW);
   else
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)wgrad_reduce_blocks(R, Cg_out)), dim3(128), 0, st, ws,
                        nsplit, R, Cg, Cg_out, dW);
@@ -304,11 +280,10 @@ static void wgrad_launch(int dtype, int pad, dim3 grid, const WgradParams& p, hi
   }
 }
 
-struct WgPlan {
-  int mtiles, ntiles, nsplit, pchunk;
-};
-static WgPlan wg_plan(int P, int R, int Cg) {
+WgPlan wg_plan(int P, int R, int Cg) {
   WgPlan pl{};
+  pl.BM = WG_BM;
+  pl.BN = WG_BN;
   pl.mtiles = cdiv(R, WG_BM);
   pl.ntiles = cdiv(16LL * Cg, WG_BN);
   const long long tiles = (long long)pl.mtiles * pl.ntiles;
@@ -541,66 +516,94 @@ __global__ void __launch_bounds__(256) wgrad_rows_mfma_kernel(const char* __rest
     for (int e = 0; e < 4; ++e) slab[((long long)r * 16 + 4 * kq + e) * Cg + ci] = acc[r][e];
 }
 
+// ---- the rows kernels' conditions: stc_conv_wgrad_rows requires them, wgrad_rows_kind tests them
+static bool rows_count_ok(int R_out, int R) { return R_out >= 1 && R_out <= 2 && R_out <= R; }
+static bool rows_views_ok(const stc_view& D, const stc_view& G, int Cg, int Cg_out) {
+  return Cg % 64 == 0 && Cg_out <= Cg && G.cs == 1 && G.co % 4 == 0 && G.ps % 4 == 0 && D.cs == 1;
+}
+static bool rows_geometry_ok(const stc_view& D, const stc_view& G) { return D.H == G.H - 1 && D.W == G.W - 1; }
+
+WgradKernel wgrad_rows_kind(const WgradAsk& a, WgradRoute& r) {
+  const stc_view &D = a.D, &G = a.G;
+  const int R_out = a.rows;
+  if (!((a.dtype == STC_F32 || a.dtype == STC_BF16) && rows_count_ok(R_out, a.R) &&
+        rows_views_ok(D, G, a.Cg, a.Cg_out) && rows_geometry_ok(D, G)))
+    return WG_NONE;
+  // bf16 on MFMA (wgrad_rows_mfma_kernel): input <= 32 x 32 (rows of 32 slots), 16-byte aligned input channels
+  const int parts = (G.H + WRM_ROWS - 1) / WRM_ROWS;
+  const size_t lds_m = (size_t)WRM_ROWS * WRM_W * 128 + (size_t)R_out * 4 * (D.H + 5) * WRM_PITCH * 2;
+  const long long g_bytes = (long long)a.B * G.bs * 2;
+  if (a.dtype == STC_BF16 && G.ps % 8 == 0 && G.co % 8 == 0 && G.W <= WRM_W && G.H <= 32 && parts <= 4 &&
+      R_out * D.H * D.W <= 256 * WRM_DPT &&
+      lds_m <= 96 * 1024 && g_bytes < (1ll << 31)) {
+    r.rows_parts = parts;
+    r.lds = lds_m;
+    return WG_ROWS_MFMA;
+  }
+  r.rows_parts = 4;  // the VALU kernel's pixel splits (PS)
+  r.lds = ((((size_t)R_out * (D.H + 4) * (D.W + 4) + 3) & ~(size_t)3) + (size_t)16 * R_out * 16 * 64) * 4;
+  return WG_ROWS;  // (stc_conv_wgrad_rows refuses a D plane too large for LDS; the automatic budget is well inside)
+}
+
 }  // namespace stc
 
 using namespace stc;
 
 extern "C" int64_t stc_conv_wgrad_rows_workspace(int B, int IH, int R_out, int Cg) {
   (void)IH;
-  return (int64_t)B * 4 * R_out * 16LL * Cg * 4;  // a slab per (image, pixel split)
+  return wgrad_slab_bytes(B * 4, R_out, Cg);  // a slab per (image, pixel split)
 }
 
 extern "C" int stc_conv_wgrad_rows(int dtype, int B, stc_view D, int R, int R_out, stc_view G, int Cg, int Cg_out,
                                    float* dW, void* workspace, int64_t workspace_bytes, void* stream) {
   STC_REQUIRE(dtype == STC_F32 || dtype == STC_BF16, "stc_conv_wgrad_rows: bad dtype");
-  STC_REQUIRE(R_out >= 1 && R_out <= 2 && R_out <= R, "stc_conv_wgrad_rows: R_out=%d (1..2, <= R)", R_out);
-  STC_REQUIRE(Cg % 64 == 0 && Cg_out <= Cg && G.cs == 1 && G.co % 4 == 0 && G.ps % 4 == 0 && D.cs == 1,
+  STC_REQUIRE(rows_count_ok(R_out, R), "stc_conv_wgrad_rows: R_out=%d (1..2, <= R)", R_out);
+  STC_REQUIRE(rows_views_ok(D, G, Cg, Cg_out),
               "stc_conv_wgrad_rows: Cg=%d / views (NHWC, Cg a multiple of 64, 4-channel aligned)", Cg);
-  STC_REQUIRE(D.H == G.H - 1 && D.W == G.W - 1, "stc_conv_wgrad_rows: stride-1 4x4 geometry needs D = G - 1 (%dx%d vs %dx%d)",
+  STC_REQUIRE(rows_geometry_ok(D, G), "stc_conv_wgrad_rows: stride-1 4x4 geometry needs D = G - 1 (%dx%d vs %dx%d)",
               D.H, D.W, G.H, G.W);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t need = stc_conv_wgrad_rows_workspace(B, G.H, R_out, Cg);
-  // bf16 on MFMA (wgrad_rows_mfma_kernel): input <= 32 x 32 (rows of 32 slots), 16-byte aligned input channels
-  const int parts = (G.H + WRM_ROWS - 1) / WRM_ROWS;
-  const size_t lds_m = (size_t)WRM_ROWS * WRM_W * 128 + (size_t)R_out * 4 * (D.H + 5) * WRM_PITCH * 2;
-  const long long g_bytes = (long long)B * G.bs * 2;
-  if (dtype == STC_BF16 && G.ps % 8 == 0 && G.co % 8 == 0 && G.W <= WRM_W && G.H <= 32 && parts <= 4 &&
-      R_out * D.H * D.W <= 256 * WRM_DPT &&
-      lds_m <= 96 * 1024 && g_bytes < (1ll << 31)) {
-    STC_REQUIRE(workspace && workspace_bytes >= need, "stc_conv_wgrad_rows: workspace %lld < %lld",
-                (long long)workspace_bytes, (long long)need);
-    float* ws = (float*)workspace;
-    const dim3 grid((unsigned)(B * (Cg / 64) * parts));
+  WgradAsk a{};
+  a.dtype = dtype; a.B = B; a.stride = 1; a.D = D; a.G = G; a.R = R; a.Cg = Cg; a.Cg_out = Cg_out;
+  a.rows = R_out; a.rows_direct = true; a.pad = STC_PAD_ZEROS;
+  const WgradRoute r = wgrad_route(a);
+  if (r.kernel == WG_NONE) {  // no pixels
+    (void)hipMemsetAsync(dW, 0, (size_t)R * Cg_out * 16 * 4, st);
+    STC_CHECK_LAUNCH();
+    return 0;
+  }
+  STC_REQUIRE(workspace && workspace_bytes >= r.ws_bytes, "stc_conv_wgrad_rows: workspace %lld < %lld",
+              (long long)workspace_bytes, (long long)r.ws_bytes);
+  float* ws = (float*)workspace;
+  if (r.kernel == WG_ROWS_MFMA) {
+    const dim3 grid((unsigned)(B * (Cg / 64) * r.rows_parts));
+    const long long g_bytes = (long long)B * G.bs * 2;
     main_timer_begin(st);
 #define STC_WRM(RO_)                                                                                               \
-  hipLaunchKernelGGL((wgrad_rows_mfma_kernel<RO_>), grid, dim3(256), lds_m, st, (const char*)D.p, D.bs, D.rs, D.ps, \
+  hipLaunchKernelGGL((wgrad_rows_mfma_kernel<RO_>), grid, dim3(256), r.lds, st, (const char*)D.p, D.bs, D.rs, D.ps, \
                      D.co, D.H, D.W, (const char*)G.p, (unsigned)g_bytes, (int)G.bs, (int)G.rs, G.ps, G.co, G.H, G.W,  \
-                     Cg, parts, ws, dW + (size_t)R_out * Cg_out * 16, (long long)(R - R_out) * Cg_out * 16)
+                     Cg, r.rows_parts, ws, dW + (size_t)R_out * Cg_out * 16, (long long)(R - R_out) * Cg_out * 16)
     if (R_out == 1) STC_WRM(1);
     else STC_WRM(2);
 #undef STC_WRM
     main_timer_end(st);
     STC_CHECK_LAUNCH();
-    wgrad_reduce_launch(ws, B * parts, R_out, Cg, Cg_out, dW, st);
+    wgrad_reduce_launch(r.reduce, ws, r.slabs, R_out, Cg, Cg_out, dW, st);
     STC_CHECK_LAUNCH();
     return 0;
   }
   const int blocks = B * (Cg / 64) * 4;
-  STC_REQUIRE(workspace && workspace_bytes >= need, "stc_conv_wgrad_rows: workspace %lld < %lld",
-              (long long)workspace_bytes, (long long)need);
-  const size_t lds = ((((size_t)R_out * (D.H + 4) * (D.W + 4) + 3) & ~(size_t)3) + (size_t)16 * R_out * 16 * 64) * 4;
-  STC_REQUIRE(lds <= 160 * 1024, "stc_conv_wgrad_rows: D plane too large for LDS (%dx%d)", D.H, D.W);
-  float* ws = (float*)workspace;
+  STC_REQUIRE(r.lds <= 160 * 1024, "stc_conv_wgrad_rows: D plane too large for LDS (%dx%d)", D.H, D.W);
   main_timer_begin(st);
 #define STC_WR(T_, RO_)                                                                                          \
-  hipLaunchKernelGGL((wgrad_rows_kernel<T_, RO_>), dim3(blocks), dim3(256), lds, st, (const char*)D.p, D.bs,    \
+  hipLaunchKernelGGL((wgrad_rows_kernel<T_, RO_>), dim3(blocks), dim3(256), r.lds, st, (const char*)D.p, D.bs,  \
                      D.rs, D.ps, D.co, D.H, D.W, (const char*)G.p, G.bs, G.rs, G.ps, G.co, G.H, G.W, Cg, ws)
   if (dtype == STC_BF16) { if (R_out == 1) STC_WR(bf16, 1); else STC_WR(bf16, 2); }
   else { if (R_out == 1) STC_WR(float, 1); else STC_WR(float, 2); }
 #undef STC_WR
   main_timer_end(st);
   STC_CHECK_LAUNCH();
-  wgrad_reduce_launch(ws, B * 4, R_out, Cg, Cg_out, dW, st);
+  wgrad_reduce_launch(r.reduce, ws, r.slabs, R_out, Cg, Cg_out, dW, st);
   STC_CHECK_LAUNCH();
   if (R > R_out) {  // the zero rows of the padded D channels
     (void)hipMemsetAsync(dW + (size_t)R_out * Cg_out * 16, 0, (size_t)(R - R_out) * Cg_out * 16 * 4, st);
@@ -609,20 +612,43 @@ extern "C" int stc_conv_wgrad_rows(int dtype, int B, stc_view D, int R, int R_ou
   return 0;
 }
 
+// ---- asks
+static WgradAsk wgrad_ask(int dtype, int B, int stride, const stc_view& D, int R, const stc_view& G, int Cg, int Cg_out,
+                          bool prologue, int pad, const int32_t* force) {
+  WgradAsk a{};
+  a.dtype = dtype; a.B = B; a.stride = stride; a.D = D; a.G = G; a.R = R; a.Cg = Cg; a.Cg_out = Cg_out;
+  a.prologue = prologue; a.pad = pad; a.force = force;
+  return a;
+}
+
+// The stride-less queries take a D grid and no views, stride or prologue.  What they assume, written down once: dense
+// NHWC views with every channel wanted (Cg_out = Cg), channel offset 0 and batch stride 0 -- a shape has no allocation,
+// so the 2 GiB limits of the bf16 kernels count as met -- and no rows kernel.
+// * Plan reported = the stride-2 plan with G on the doubled grid; on the 31-wide grids that only the stride-1 halo tile
+//   plans for (over its virtual grid), the stride-1 plan with G on the grid + 1.
+// * Workspace = enough for every call on that D grid: stride 2 and stride 1, with or without a prologue (the
+//   register-staged kernel).  (A G off its stride's grid takes the halo tile out, and a plan without it does not depend
+//   on the stride: it is the stride-1 plan on the stride-2 halo grids, the stride-2 plan on the 31-wide ones.)
+// * bf16 shapes the LDS-DMA kernels refuse even on dense views (R or Cg no multiple of 8, 2^24 pixels or more) are
+//   answered for the register-staged kernel that runs.
+static void wgrad_shape_answer(int dtype, int B, int Hd, int Wd, int R, int Cg, int pad, const int32_t* force,
+                               int64_t* workspace_bytes, int32_t* plan_out) {
+  const stc_view D = dense_view(Hd, Wd, R);
+  auto route = [&](int stride, int GH, int GW, bool prologue) {
+    return wgrad_route(wgrad_ask(dtype, B, stride, D, R, dense_view(GH, GW, Cg), Cg, Cg, prologue, pad, force));
+  };
+  const WgradRoute s2 = route(2, 2 * Hd, 2 * Wd, false), s1 = route(1, Hd + 1, Wd + 1, false);
+  const WgradRoute pro = route(2, 2 * Hd, 2 * Wd, true);
+  if (workspace_bytes) *workspace_bytes = std::max(std::max(s2.ws_bytes, s1.ws_bytes), pro.ws_bytes);
+  if (plan_out) {
+    const WgradRoute& r = s1.wb.s1v ? s1 : s2;
+    for (int i = 0; i < 5; ++i) plan_out[i] = r.plan[i];
+  }
+}
+
 extern "C" int stc_conv_wgrad_query(int dtype, int B, int Hd, int Wd, int R, int Cg, const int32_t* force_plan,
                                     int64_t* workspace_bytes, int32_t* plan_out) {
-  const WgPlan pl = wg_plan(B * Hd * Wd, R, Cg);
-  const int64_t ws_reg = pl.nsplit <= 1 ? 0 : (int64_t)pl.nsplit * R * 16LL * Cg * 4;  // 0: straight into dW
-  // bf16 without prologues runs the LDS-DMA kernel (wgrad_bf16.hip); the prologue form the register-staged one
-  const int64_t ws_dma = dtype == STC_BF16 ? wgrad_bf16_workspace(B, Hd, Wd, R, Cg, force_plan) : 0;
-  if (workspace_bytes) *workspace_bytes = std::max(ws_reg, ws_dma);
-  if (plan_out) {
-    if (dtype == STC_BF16) {
-      wgrad_bf16_plan(B, Hd, Wd, R, Cg, force_plan, plan_out);
-    } else {
-      plan_out[0] = -1; plan_out[1] = WG_BM; plan_out[2] = WG_BN; plan_out[3] = pl.nsplit; plan_out[4] = pl.nsplit > 1;
-    }
-  }
+  wgrad_shape_answer(dtype, B, Hd, Wd, R, Cg, STC_PAD_ZEROS, force_plan, workspace_bytes, plan_out);
   return 0;
 }
 
@@ -630,6 +656,29 @@ extern "C" int64_t stc_conv_wgrad_workspace(int dtype, int B, int Hd, int Wd, in
   int64_t ws = 0;
   stc_conv_wgrad_query(dtype, B, Hd, Wd, R, Cg, nullptr, &ws, nullptr);
   return ws;
+}
+
+// The route of a call's actual views and stride: workspace bytes, plan_out[5] as stc_conv_wgrad_query reports it,
+// kernel_out[2] = {WgradKernel, WgradReduce}, the kernel's name.  rows: the real channels of D (0: the rows kernels off).
+extern "C" int stc_conv_wgrad_route(int dtype, int B, int stride, stc_view D, int R, int rows, stc_view G, int Cg,
+                                    int Cg_out, int prologue, int pad_mode, const int32_t* force_plan,
+                                    int64_t* workspace_bytes, int32_t* plan_out, int32_t* kernel_out, char* name_out,
+                                    int name_cap) {
+  STC_REQUIRE(dtype == STC_F32 || dtype == STC_BF16, "stc_conv_wgrad_route: bad dtype %d", dtype);
+  STC_REQUIRE(pad_mode == STC_PAD_ZEROS || pad_mode == STC_PAD_REFLECT,
+              "stc_conv_wgrad_route: pad_mode %d is neither STC_PAD_ZEROS nor STC_PAD_REFLECT", pad_mode);
+  STC_REQUIRE(pad_mode == STC_PAD_ZEROS || !force_plan,
+              "stc_conv_wgrad_route: no plan can be forced under STC_PAD_REFLECT (force_plan must be NULL)");
+  STC_REQUIRE(rows >= 0, "stc_conv_wgrad_route: rows=%d", rows);
+  WgradAsk a = wgrad_ask(dtype, B, stride, D, R, G, Cg, Cg_out, prologue != 0, pad_mode, force_plan);
+  a.rows = rows;
+  const WgradRoute r = wgrad_route(a);
+  if (workspace_bytes) *workspace_bytes = r.ws_bytes;
+  if (plan_out)
+    for (int i = 0; i < 5; ++i) plan_out[i] = r.plan[i];
+  if (kernel_out) { kernel_out[0] = r.kernel; kernel_out[1] = r.reduce; }
+  if (name_out && name_cap > 0) snprintf(name_out, (size_t)name_cap, "%s", r.name);
+  return 0;
 }
 
 extern "C" int stc_conv_wgrad(int dtype, int B, int stride, stc_view D, int R,
@@ -655,6 +704,16 @@ static int wgrad_run(int dtype, int B, int stride, stc_view D, int R,
   STC_REQUIRE(D.cs == 1 && G.cs == 1 && D.co % VEC == 0 && G.co % VEC == 0 && D.ps % VEC == 0 && G.ps % VEC == 0,
               "stc_conv_wgrad: views must be NHWC with %d-aligned channels", VEC);
   STC_REQUIRE(Cg_out <= Cg, "stc_conv_wgrad: Cg_out > Cg");
+  hipStream_t st = (hipStream_t)stream;
+  // (the prologue as the route sees it: what keeps a bf16 call off the LDS-DMA kernels)
+  const WgradAsk a = wgrad_ask(dtype, B, stride, D, R, G, Cg, Cg_out, d_scale || d_act || g_scale || g_act, pad, force_plan);
+  const WgradRoute r = wgrad_route(a);
+  if (r.kernel == WG_NONE) {  // no pixels
+    (void)hipMemsetAsync(dW, 0, (size_t)R * Cg_out * 16 * 4, st);
+    STC_CHECK_LAUNCH();
+    return 0;
+  }
+  if (r.kernel != WG_FP_TILE) return wgrad_bf16(a, r, dW, workspace, workspace_bytes, st);
   WgradParams p{};
   p.d = (const char*)D.p; p.d_bs = D.bs; p.d_rs = D.rs; p.d_ps = D.ps; p.d_co = D.co;
   p.g = (const char*)G.p; p.g_bs = G.bs; p.g_rs = G.rs; p.g_ps = G.ps; p.g_co = G.co;
@@ -663,19 +722,11 @@ static int wgrad_run(int dtype, int B, int stride, stc_view D, int R,
   p.P = B * D.H * D.W;
   p.dsc = d_scale; p.dsh = d_shift; p.dact = d_act; p.dslope = d_slope;
   p.gsc = g_scale; p.gsh = g_shift; p.gact = g_act; p.gslope = g_slope;
-  hipStream_t st = (hipStream_t)stream;
-  if (p.P == 0) {
-    (void)hipMemsetAsync(dW, 0, (size_t)R * Cg_out * 16 * 4, st);
-    STC_CHECK_LAUNCH();
-    return 0;
-  }
-  if (!pad && dtype == STC_BF16 && !d_scale && !d_act && !g_scale && !g_act && wgrad_bf16_eligible(B, D, R, G, Cg))
-    return wgrad_bf16(B, stride, D, R, G, Cg, Cg_out, dW, workspace, workspace_bytes, st, force_plan);
-  const WgPlan pl = wg_plan(p.P, R, Cg);
+  const WgPlan& pl = r.fp;
   p.mtiles = pl.mtiles; p.ntiles = pl.ntiles; p.nsplit = pl.nsplit; p.pchunk = pl.pchunk;
   p.Cg_out = Cg_out;
   dim3 grid(pl.mtiles * pl.ntiles, 1, pl.nsplit);
-  if (pl.nsplit <= 1) {
+  if (!r.slabs) {
     p.dW = dW;
     main_timer_begin(st);
     wgrad_launch(dtype, pad, grid, p, st);
@@ -683,15 +734,14 @@ static int wgrad_run(int dtype, int B, int stride, stc_view D, int R,
     STC_CHECK_LAUNCH();
     return 0;
   }
-  const int64_t need = (int64_t)pl.nsplit * R * 16LL * Cg * 4;
-  STC_REQUIRE(workspace && workspace_bytes >= need, "stc_conv_wgrad: workspace %lld < %lld",
-              (long long)workspace_bytes, (long long)need);
+  STC_REQUIRE(workspace && workspace_bytes >= r.ws_bytes, "stc_conv_wgrad: workspace %lld < %lld",
+              (long long)workspace_bytes, (long long)r.ws_bytes);
   p.ws = (float*)workspace;
   main_timer_begin(st);
   wgrad_launch(dtype, pad, grid, p, st);
   main_timer_end(st);
   STC_CHECK_LAUNCH();
-  wgrad_reduce_launch((const float*)p.ws, pl.nsplit, R, Cg, Cg_out, dW, st);
+  wgrad_reduce_launch(r.reduce, (const float*)p.ws, pl.nsplit, R, Cg, Cg_out, dW, st);
   STC_CHECK_LAUNCH();
   return 0;
 }
@@ -723,13 +773,7 @@ static int pad_wgrad_checks(const char* who, int dtype, int kind, int pad_mode, 
 extern "C" int stc_conv_pad_wgrad_query(int dtype, int kind, int pad_mode, int B, int Hd, int Wd, int R, int Cg,
                                         const int32_t* force_plan, int64_t* workspace_bytes, int32_t* plan_out) {
   if (const int rc = pad_wgrad_checks("stc_conv_pad_wgrad_query", dtype, kind, pad_mode, force_plan)) return rc;
-  if (pad_mode == STC_PAD_ZEROS)
-    return stc_conv_wgrad_query(dtype, B, Hd, Wd, R, Cg, force_plan, workspace_bytes, plan_out);
-  const WgPlan pl = wg_plan(B * Hd * Wd, R, Cg);
-  if (workspace_bytes) *workspace_bytes = pl.nsplit <= 1 ? 0 : (int64_t)pl.nsplit * R * 16LL * Cg * 4;
-  if (plan_out) {
-    plan_out[0] = -1; plan_out[1] = WG_BM; plan_out[2] = WG_BN; plan_out[3] = pl.nsplit; plan_out[4] = pl.nsplit > 1;
-  }
+  wgrad_shape_answer(dtype, B, Hd, Wd, R, Cg, pad_mode, force_plan, workspace_bytes, plan_out);
   return 0;
 }
 

@@ -731,42 +731,35 @@ __global__ void __launch_bounds__(512, 1) wgrad_halo_kernel(const WbParams p) {
 }
 
 // ------------------------------------------------------------------------- host
-// Tile configurations: {BM (rows), BN (columns), waves, swapped}
+// Tile configurations: {BM (rows), BN (columns), wave grid WM x WN of the compute waves, swapped}
 struct WbCfg {
-  int BM, BN, waves;
+  int BM, BN, WM, WN;
   bool swap;
   int stages = 2, loaders = 0;
+  constexpr int waves() const { return WM * WN; }
 };
 constexpr WbCfg kWbCfg[] = {
-    {128, 128, 4, false},        // 0
-    {64, 128, 4, false},         // 1: R <= 64
-    {128, 16, 4, true},          // 2: R <= 16 (rows = im2col columns, columns = R)
-    {256, 256, 8, false},        // 3
-    {256, 128, 8, false},        // 4
-    {128, 256, 8, false},        // 5
-    {128, 128, 4, false, 4, 4},  // 6: + 4 loader waves, 4-stage ring
-    {128, 128, 4, false, 3, 4},  // 7: + 4 loader waves, 3-stage ring
-    {128, 256, 8, false, 4, 4},  // 8: halo (stride 2, 16 channels x 16 taps per tile; wgrad_halo_kernel)
+    {128, 128, 2, 2, false},        // 0
+    {64, 128, 1, 4, false},         // 1: R <= 64
+    {128, 16, 4, 1, true},          // 2: R <= 16 (rows = im2col columns, columns = R)
+    {256, 256, 2, 4, false},        // 3
+    {256, 128, 4, 2, false},        // 4
+    {128, 256, 2, 4, false},        // 5
+    {128, 128, 2, 2, false, 4, 4},  // 6: + 4 loader waves, 4-stage ring
+    {128, 128, 2, 2, false, 3, 4},  // 7: + 4 loader waves, 3-stage ring
+    {128, 256, 2, 4, false, 4, 4},  // 8: halo (stride 2, 16 channels x 16 taps per tile; wgrad_halo_kernel)
 };
 constexpr int WB_HALO = 8;
 constexpr int kNumWbCfg = sizeof(kWbCfg) / sizeof(kWbCfg[0]);
 
-
-struct WbPlan {
-  int cfg, BM, BN, mtiles, ntiles, nsplit, pchunk;
-  bool slab;    // partial sums go to fp32 slabs + the ordered reduce (always when nsplit > 1)
-  bool cmajor;  // channel-group-major columns (WbParams::cmajor): one split whose tiles store torch layout directly
-};
-
 // The halo tile (cfg WB_HALO) takes the stride-2 geometry on a D grid of width 16..128 (power of two; a K-step
-// = whole grid rows or half a 128-wide row), 16-channel G groups and >= 96 D rows.  stride 0 = unknown (the
-// query, which has no stride argument: it plans as stride 2 and sizes the workspace for either).
+// = whole grid rows or half a 128-wide row), 16-channel G groups and >= 96 D rows.
 // Stride 1: a 31-wide D grid (the PatchGAN layer 4 at 256 x 256), run on the virtual 32 x 32 grid.
-static bool wb_halo_s1(int GH, int GW, int stride) { return (stride == 1 || stride == 0) && GW == 31 && (GH + 1) % 2 == 0; }
+static bool wb_halo_s1(int GH, int GW, int stride) { return stride == 1 && GW == 31 && (GH + 1) % 2 == 0; }
 static bool wb_halo_ok(int GH, int GW, int stride, int R, int Cg) {
   if (Cg % 16 != 0 || R < 96) return false;
   if (wb_halo_s1(GH, GW, stride)) return true;
-  if (!(stride == 2 || stride == 0)) return false;
+  if (stride != 2) return false;
   if (!(GW == 8 || GW == 16 || GW == 32 || GW == 64 || GW == 128)) return false;
   return GH % (64 / std::min(GW, 64)) == 0;
 }
@@ -774,15 +767,15 @@ static bool wb_halo_ok(int GH, int GW, int stride, int R, int Cg) {
 // force (optional, per call: stc_conv_wgrad_ex / stc_conv_wgrad_query): {tile config, pixel splits (0 = auto; -1 =
 // auto without the channel-group-major direct store)};
 // NULL or an unknown config = the automatic plan (also the halo config where the geometry does not allow it)
-static WbPlan wb_plan(int B, int GH, int GW, int stride, int R, int Cg, const int32_t* force) {
+WbPlan wb_plan(int B, int GH, int GW, int stride, bool g_on_grid, int R, int Cg, const int32_t* force) {
   WbPlan pl{};
   const long long ncol = 16LL * Cg;
-  const bool halo = wb_halo_ok(GH, GW, stride, R, Cg);
+  const bool halo = g_on_grid && wb_halo_ok(GH, GW, stride, R, Cg);
   int cfg = force ? force[0] : -1;
   int force_ns = force ? std::max(force[1], 0) : 0;
   if (cfg == WB_HALO && !halo) cfg = -1;
-  const bool s1v = halo && wb_halo_s1(GH, GW, stride) && (cfg < 0 || cfg >= kNumWbCfg || cfg == WB_HALO);
-  const int P = s1v ? B * (GH + 1) * (GW + 1) : B * GH * GW;  // (the stride-1 halo: its virtual grid)
+  pl.s1v = halo && wb_halo_s1(GH, GW, stride) && (cfg < 0 || cfg >= kNumWbCfg || cfg == WB_HALO);
+  const int P = pl.s1v ? B * (GH + 1) * (GW + 1) : B * GH * GW;  // (the stride-1 halo: its virtual grid)
   const int steps = cdiv(P, WB_BK);
   if (cfg < 0 || cfg >= kNumWbCfg) {
     force_ns = 0;
@@ -814,7 +807,7 @@ static WbPlan wb_plan(int B, int GH, int GW, int stride, int R, int Cg, const in
   } else {
     // about 2 four-wave blocks (one eight-wave block; 4 of the short swapped tile) per CU, at least
     // 8 K-steps (512 pixels) per split
-    const long long target = (c.waves == 8 || c.loaders) ? 256 : (c.swap ? 1024 : 512);
+    const long long target = (c.waves() == 8 || c.loaders) ? 256 : (c.swap ? 1024 : 512);
     while (tiles * ns < target && ns * 2 <= 256 && steps / (ns * 2) >= 8) ns *= 2;
   }
   pl.pchunk = cdiv(steps, ns) * WB_BK;
@@ -831,8 +824,6 @@ static WbPlan wb_plan(int B, int GH, int GW, int stride, int R, int Cg, const in
   if (pl.cmajor) pl.slab = false;
   return pl;
 }
-static int64_t wb_ws(const WbPlan& pl, int R, int Cg) { return pl.slab ? (int64_t)pl.nsplit * R * 16LL * Cg * 4 : 0; }
-
 bool wgrad_bf16_eligible(int B, const stc_view& D, int R, const stc_view& G, int Cg) {
   const long long dbytes = (long long)B * D.bs * 2, gbytes = (long long)B * G.bs * 2;
   const long long P = (long long)B * D.H * D.W;
@@ -840,81 +831,102 @@ bool wgrad_bf16_eligible(int B, const stc_view& D, int R, const stc_view& G, int
          G.ps % 8 == 0 && dbytes < (1ll << 31) && gbytes < (1ll << 31) && P < (1 << 24);
 }
 
-int64_t wgrad_bf16_workspace(int B, int Hd, int Wd, int R, int Cg, const int32_t* force) {
-  // (no stride here: enough for the stride-2 plan and for the stride-1 one)
-  return std::max(wb_ws(wb_plan(B, Hd, Wd, 0, R, Cg, force), R, Cg), wb_ws(wb_plan(B, Hd, Wd, 1, R, Cg, force), R, Cg));
+void wb_launch_shape(int GH, int GW, WgradRoute& r) {
+  const WbPlan& pl = r.wb;
+  const WbCfg& c = kWbCfg[pl.cfg];
+  auto lg2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; };
+  const int ghw = GH * GW, lgw = lg2(GW), lghw = lg2(ghw);
+  r.pmode = 0;
+  if (GW % WB_BK == 0) r.pmode = 1;
+  else if (lgw >= 0 && ghw % WB_BK == 0) r.pmode = 2;
+  else if (lghw >= 0 && lgw >= 0 && WB_BK % ghw == 0) r.pmode = 3;
+  r.lg_gw = lgw < 0 ? 0 : lgw;
+  r.lg_ghw = lghw < 0 ? 0 : lghw;
+  r.halo_s1 = pl.cfg == WB_HALO && pl.s1v;  // (the halo tile is planned on the virtual grid exactly at stride 1)
+  r.GH = r.halo_s1 ? GH + 1 : GH;
+  r.GW = r.halo_s1 ? GW + 1 : GW;
+  r.halo_tc = std::min(r.GW, 64);
+  const int htc = r.halo_tc;
+  const bool fast = r.pmode && pl.cfg != 3;  // (the fast addressing would spill the 256-VGPR tile 3)
+  if (pl.cfg == WB_HALO) {
+    r.kernel = WG_HALO;
+    r.lds = (size_t)4 * (r.halo_s1 ? WhGeom<32, true>::STAGE : htc == 64 ? WhGeom<64>::STAGE
+                                 : htc == 32 ? WhGeom<32>::STAGE
+                                 : htc == 16 ? WhGeom<16>::STAGE : WhGeom<8>::STAGE);
+    snprintf(r.name, sizeof r.name, "wgrad_halo_kernel<%d, %s>", r.halo_s1 ? 32 : htc, r.halo_s1 ? "true" : "false");
+    return;
+  }
+  r.lds = (size_t)c.stages * WB_BK * (pl.BM + pl.BN) * 2;
+  if (c.loaders) {
+    r.kernel = WG_BF16_LD;
+    snprintf(r.name, sizeof r.name, "wgrad_bf16_ld_kernel<%d, %d, %d, %d, %s, %s, %d, %d>", c.BM, c.BN, c.WM, c.WN,
+             c.swap ? "true" : "false", fast ? "true" : "false", c.loaders, c.stages);
+  } else {
+    r.kernel = WG_BF16_TILE;
+    snprintf(r.name, sizeof r.name, "wgrad_bf16_kernel<%d, %d, %d, %d, %s, %s>", c.BM, c.BN, c.WM, c.WN,
+             c.swap ? "true" : "false", fast ? "true" : "false");
+  }
 }
 
-// plan_out = {tile config, BM, BN, pixel splits, slab (1: slabs + reduce kernel)}
-void wgrad_bf16_plan(int B, int Hd, int Wd, int R, int Cg, const int32_t* force, int32_t* plan_out) {
-  const WbPlan pl = wb_plan(B, Hd, Wd, 0, R, Cg, force);  // (the stride-2 plan)
-  plan_out[0] = pl.cfg; plan_out[1] = pl.BM; plan_out[2] = pl.BN; plan_out[3] = pl.nsplit; plan_out[4] = pl.slab;
-}
-
-int wgrad_bf16(int B, int stride, stc_view D, int R, stc_view G, int Cg, int Cg_out, float* dW, void* workspace,
-               int64_t workspace_bytes, hipStream_t st, const int32_t* force) {
+int wgrad_bf16(const WgradAsk& a, const WgradRoute& r, float* dW, void* workspace, int64_t workspace_bytes,
+               hipStream_t st) {
+  const stc_view &D = a.D, &G = a.G;
+  const int B = a.B, R = a.R, Cg = a.Cg;
+  const WbPlan& pl = r.wb;
   WbParams p{};
   p.d = (const char*)D.p; p.d_bytes = (unsigned)((long long)B * D.bs * 2);
   p.d_bs = (int)D.bs; p.d_rs = (int)D.rs; p.d_ps = D.ps; p.d_co = D.co;
   p.g = (const char*)G.p; p.g_bytes = (unsigned)((long long)B * G.bs * 2);
   p.g_bs = (int)G.bs; p.g_rs = (int)G.rs; p.g_ps = G.ps; p.g_co = G.co;
-  p.GH = D.H; p.GW = D.W; p.IH = G.H; p.IW = G.W; p.stride = stride;
-  p.R = R; p.Cg = Cg; p.Ncol = 16 * Cg; p.Cg_out = Cg_out;
-  p.P = B * D.H * D.W;
+  p.GH = r.GH; p.GW = r.GW; p.IH = G.H; p.IW = G.W; p.stride = a.stride;
+  p.R = R; p.Cg = Cg; p.Ncol = 16 * Cg; p.Cg_out = a.Cg_out;
+  p.P = B * r.GH * r.GW;
   p.inv_ghw = 1.0f / (float)(D.H * D.W);
   p.inv_gw = 1.0f / (float)D.W;
-  {
-    auto lg2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; };
-    const int ghw = D.H * D.W, lgw = lg2(D.W), lghw = lg2(ghw);
-    p.pmode = 0;
-    if (D.W % WB_BK == 0) p.pmode = 1;
-    else if (lgw >= 0 && ghw % WB_BK == 0) p.pmode = 2;
-    else if (lghw >= 0 && lgw >= 0 && WB_BK % ghw == 0) p.pmode = 3;
-    p.lg_gw = lgw < 0 ? 0 : lgw;
-    p.lg_ghw = lghw < 0 ? 0 : lghw;
-  }
-  // (the stride-2 halo tile needs G on exactly the doubled grid, the stride-1 one on the grid + 1)
-  const bool g2x = G.H == 2 * D.H && G.W == 2 * D.W, g1x = G.H == D.H + 1 && G.W == D.W + 1;
-  const WbPlan pl = wb_plan(B, D.H, D.W, stride == 2 ? (g2x ? 2 : -1) : (g1x ? 1 : -1), R, Cg, force);
-  const bool hs1 = pl.cfg == WB_HALO && stride == 1;
-  if (hs1) {  // the virtual grid
-    p.GH = D.H + 1; p.GW = D.W + 1;
-    p.P = B * p.GH * p.GW;
-  }
+  p.pmode = r.pmode; p.lg_gw = r.lg_gw; p.lg_ghw = r.lg_ghw;
   p.mtiles = pl.mtiles; p.ntiles = pl.ntiles; p.nsplit = pl.nsplit; p.pchunk = pl.pchunk;
   p.cmajor = pl.cmajor ? 1 : 0;
   dim3 grid(pl.mtiles * pl.ntiles, 1, pl.nsplit);
-  const int htc = std::min(p.GW, 64);
-  const size_t lds = pl.cfg == WB_HALO
-                         ? (size_t)4 * (hs1 ? WhGeom<32, true>::STAGE : htc == 64 ? WhGeom<64>::STAGE
-                                                                       : htc == 32 ? WhGeom<32>::STAGE
-                                                                       : htc == 16 ? WhGeom<16>::STAGE : WhGeom<8>::STAGE)
-                         : (size_t)kWbCfg[pl.cfg].stages * WB_BK * (pl.BM + pl.BN) * 2;
+  const bool hs1 = r.halo_s1;
+  const int htc = r.halo_tc;
+  const size_t lds = r.lds;
   if (!pl.slab) {
     p.dW = dW;
   } else {
-    const int64_t need = (int64_t)pl.nsplit * R * 16LL * Cg * 4;
+    const int64_t need = wgrad_slab_bytes(pl.nsplit, R, Cg);
     STC_REQUIRE(workspace && workspace_bytes >= need, "wgrad bf16: workspace %lld < %lld", (long long)workspace_bytes,
                 (long long)need);
     p.ws = (float*)workspace;
   }
   main_timer_begin(st);
-#define STC_WB(BM_, BN_, WM_, WN_, SW_, T_)                                                                   \
-  if (p.pmode) hipLaunchKernelGGL((wgrad_bf16_kernel<BM_, BN_, WM_, WN_, SW_, true>), grid, dim3(T_), lds, st, p); \
-  else hipLaunchKernelGGL((wgrad_bf16_kernel<BM_, BN_, WM_, WN_, SW_, false>), grid, dim3(T_), lds, st, p);
+  // every case checks its template arguments against the tile table, from which wb_launch_shape builds the name
+#define STC_WB_IS(C_, BM_, BN_, WM_, WN_, SW_, LD_, NST_)                                                        \
+  static_assert(kWbCfg[C_].BM == BM_ && kWbCfg[C_].BN == BN_ && kWbCfg[C_].WM == WM_ && kWbCfg[C_].WN == WN_ &&  \
+                    kWbCfg[C_].swap == SW_ && kWbCfg[C_].loaders == LD_ && kWbCfg[C_].stages == NST_,            \
+                "wgrad_bf16: a launch's template arguments differ from kWbCfg")
+#define STC_WB(C_, BM_, BN_, WM_, WN_, SW_, T_)                                                                    \
+  case C_: {                                                                                                       \
+    STC_WB_IS(C_, BM_, BN_, WM_, WN_, SW_, 0, 2);                                                                  \
+    if (p.pmode) hipLaunchKernelGGL((wgrad_bf16_kernel<BM_, BN_, WM_, WN_, SW_, true>), grid, dim3(T_), lds, st, p); \
+    else hipLaunchKernelGGL((wgrad_bf16_kernel<BM_, BN_, WM_, WN_, SW_, false>), grid, dim3(T_), lds, st, p);      \
+  } break;
+#define STC_WBL(C_, NST_)                                                                                          \
+  case C_: {                                                                                                       \
+    STC_WB_IS(C_, 128, 128, 2, 2, false, 4, NST_);                                                                 \
+    if (p.pmode) hipLaunchKernelGGL((wgrad_bf16_ld_kernel<128, 128, 2, 2, false, true, 4, NST_>), grid, dim3(512), lds, st, p); \
+    else hipLaunchKernelGGL((wgrad_bf16_ld_kernel<128, 128, 2, 2, false, false, 4, NST_>), grid, dim3(512), lds, st, p); \
+  } break;
   switch (pl.cfg) {
-    case 0: STC_WB(128, 128, 2, 2, false, 256) break;
-    case 1: STC_WB(64, 128, 1, 4, false, 256) break;
-    case 2: STC_WB(128, 16, 4, 1, true, 256) break;
+    STC_WB(0, 128, 128, 2, 2, false, 256)
+    STC_WB(1, 64, 128, 1, 4, false, 256)
+    STC_WB(2, 128, 16, 4, 1, true, 256)
     case 3:  // (the fast addressing would spill this 256-VGPR kernel: it keeps the per-step division)
+      STC_WB_IS(3, 256, 256, 2, 4, false, 0, 2);
       hipLaunchKernelGGL((wgrad_bf16_kernel<256, 256, 2, 4, false, false>), grid, dim3(512), lds, st, p);
       break;
-    case 4: STC_WB(256, 128, 4, 2, false, 512) break;
-    case 5: STC_WB(128, 256, 2, 4, false, 512) break;
-    case 6:
-      if (p.pmode) hipLaunchKernelGGL((wgrad_bf16_ld_kernel<128, 128, 2, 2, false, true, 4, 4>), grid, dim3(512), lds, st, p);
-      else hipLaunchKernelGGL((wgrad_bf16_ld_kernel<128, 128, 2, 2, false, false, 4, 4>), grid, dim3(512), lds, st, p);
-      break;
+    STC_WB(4, 256, 128, 4, 2, false, 512)
+    STC_WB(5, 128, 256, 2, 4, false, 512)
+    STC_WBL(6, 4)
     case WB_HALO:
       if (hs1) hipLaunchKernelGGL((wgrad_halo_kernel<32, true>), grid, dim3(512), lds, st, p);
       else if (htc == 64) hipLaunchKernelGGL((wgrad_halo_kernel<64, false>), grid, dim3(512), lds, st, p);
@@ -923,15 +935,15 @@ int wgrad_bf16(int B, int stride, stc_view D, int R, stc_view G, int Cg, int Cg_
       else hipLaunchKernelGGL((wgrad_halo_kernel<8, false>), grid, dim3(512), lds, st, p);
       break;
     default:
-      if (p.pmode) hipLaunchKernelGGL((wgrad_bf16_ld_kernel<128, 128, 2, 2, false, true, 4, 3>), grid, dim3(512), lds, st, p);
-      else hipLaunchKernelGGL((wgrad_bf16_ld_kernel<128, 128, 2, 2, false, false, 4, 3>), grid, dim3(512), lds, st, p);
-      break;
+    STC_WBL(7, 3)
   }
+#undef STC_WBL
+#undef STC_WB_IS
 #undef STC_WB
   main_timer_end(st);
   STC_CHECK_LAUNCH();
   if (!pl.slab) return 0;
-  wgrad_reduce_launch((const float*)p.ws, pl.nsplit, R, Cg, Cg_out, dW, st);
+  wgrad_reduce_launch(r.reduce, (const float*)p.ws, pl.nsplit, R, Cg, a.Cg_out, dW, st);
   STC_CHECK_LAUNCH();
   return 0;
 }

@@ -26,6 +26,8 @@ HEADS = {"none": HEAD_NONE, "tanh": HEAD_TANH, "sigmoid": HEAD_SIGMOID, "htanh":
 # STC_PAD_*: the padding mode of a Conv2d k4 p1 (stc_conv_pad_fwd / _dgrad / _wgrad)
 PAD_ZEROS, PAD_REFLECT = 0, 1
 PADS = {"zeros": PAD_ZEROS, "reflect": PAD_REFLECT}
+# WgradKernel (csrc/conv_route.hpp): the kernel stc_conv_wgrad_route names
+WG_NONE, WG_FP_TILE, WG_BF16_TILE, WG_BF16_LD, WG_HALO, WG_ROWS, WG_ROWS_MFMA = range(7)
 
 
 def head_code(act):
@@ -170,6 +172,8 @@ _SIGS = {
     "stc_adam_elems_per_block": (_i32, []),
     "stc_conv_wgrad_rows": (_i32, [_i32, _i32, View, _i32, _i32, View, _i32, _i32, _vp, _vp, _i64, _vp]),
     "stc_conv_wgrad_rows_workspace": (_i64, [_i32, _i32, _i32, _i32]),
+    "stc_conv_wgrad_route": (_i32, [_i32, _i32, _i32, View, _i32, _i32, View, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                    _vp, _i32]),
     "stc_adam_pack_step": (_i32, [_vp, _i32, _i64, _f32, _f32, _f32, _f32, _i32, _vp]),
     "stc_adam_pack_step_dev": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _f32, _f32, _f32, _vp]),
     "stc_adam_coef_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),

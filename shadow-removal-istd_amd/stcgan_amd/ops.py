@@ -539,13 +539,6 @@ def bn_finalize_part(part, nch, C, bn, scale_out, shift_out, update_running=True
     return mean, rstd
 
 
-# bf16 weight-gradient tile configurations (csrc/wgrad_bf16.hip kWbCfg): cfg -> (BM, BN, WM, WN, swapped)
-_WB_TILES = [(128, 128, 2, 2, "false"), (64, 128, 1, 4, "false"), (128, 16, 4, 1, "true"), (256, 256, 2, 4, "false"),
-             (256, 128, 4, 2, "false"), (128, 256, 2, 4, "false"), (128, 128, 2, 2, "false", 4, 4),
-             (128, 128, 2, 2, "false", 4, 3),
-             (128, 256, 2, 2, "false", -2, 4)]  # (BM, BN, WM, WN, swapped[, loader waves (-2: halo), stages])
-
-
 def wgrad_query(B, Hd, Wd, R, Cg, dt, force=None):
     """(workspace bytes, plan (cfg, BM, BN, splits, slab)) of stc_conv_wgrad_ex for these arguments."""
     key = ("wq", B, Hd, Wd, R, Cg, dt, None if force is None else tuple(force))
@@ -559,23 +552,6 @@ def wgrad_query(B, Hd, Wd, R, Cg, dt, force=None):
           "stc_conv_wgrad_query")
     r = _MEMO[key] = (ws.value, tuple(po))
     return r
-
-
-def _wgrad_kernel_name(plan, Hd, Wd):
-    cfg = plan[0]
-    if cfg < 0:
-        return "wgrad_kernel"
-    bm, bn, wm, wn, sw = _WB_TILES[cfg][:5]
-    ld, nst = _WB_TILES[cfg][5:] if len(_WB_TILES[cfg]) > 5 else (0, 2)
-    ghw = Hd * Wd
-    pow2 = lambda v: v > 0 and (v & (v - 1)) == 0  # noqa: E731
-    fast = Wd % 64 == 0 or (pow2(Wd) and ghw % 64 == 0) or (pow2(ghw) and pow2(Wd) and 64 % ghw == 0)
-    fast = fast and cfg != 3  # the 256x256 tile keeps the general addressing (register budget)
-    if ld == -2:  # (the stride-1 halo tile: a 31-wide grid run as 32 x 32)
-        return "wgrad_halo_kernel<32, true>" if Wd == 31 else f"wgrad_halo_kernel<{min(Wd, 64)}, false>"
-    if ld:
-        return f"wgrad_bf16_ld_kernel<{bm}, {bn}, {wm}, {wn}, {sw}, {str(fast).lower()}, {ld}, {nst}>"
-    return f"wgrad_bf16_kernel<{bm}, {bn}, {wm}, {wn}, {sw}, {str(fast).lower()}>"
 
 
 # The narrow-R weight gradient (stc_conv_wgrad_rows) for the PatchGAN logits layer: bf16 on the MFMA rows kernel
@@ -614,58 +590,55 @@ def wgrad_pad_query(stride, B, Hd, Wd, R, Cg, dt, pad, force=None):
     return r
 
 
+def _wgrad_route(B, stride, Dv, R, Gv, Cg, Cg_out, dt, rows=0, prologue=False, pad=L.PAD_ZEROS, force=None):
+    """(workspace bytes, plan (cfg, BM, BN, slabs, slab), kernel (L.WG_*), reduce, kernel name) of one weight-gradient
+    call, for its views and stride: stc_conv_wgrad_route (csrc/wgrad_route.cpp decides, nothing here does)."""
+    key = ("wr", B, R, Cg, Cg_out, dt, L.layout_key(Dv), L.layout_key(Gv), stride, rows, prologue, pad,
+           None if force is None else tuple(force))
+    r = _MEMO.get(key)
+    if r is None:
+        ws, po, ko = ctypes.c_int64(), (ctypes.c_int32 * 5)(), (ctypes.c_int32 * 2)()
+        name = ctypes.create_string_buffer(96)
+        fp = (ctypes.c_int32 * 2)(*force) if force is not None else None
+        check(lib().stc_conv_wgrad_route(L.dtype_code(dt), B, stride, Dv, R, rows, Gv, Cg, Cg_out, int(prologue), pad, fp,
+                                         ctypes.byref(ws), po, ko, name, 96), "stc_conv_wgrad_route")
+        r = _MEMO[key] = (ws.value, tuple(po), ko[0], ko[1], name.value.decode())
+    return r
+
+
 def wgrad(B, stride, Dv, R, Gv, Cg, Cg_out, dt, dpro=None, dslope=None, gpro=None, gslope=None, device=None,
           force=None, rows=None, rows_kernel=None, out=None, pad=L.PAD_ZEROS):
-    """Weight gradient [R][Cg_out][4][4] fp32 (stc_conv_wgrad_ex; force = optional {tile config, splits}),
-    written into ``out`` when given (e.g. a view of a flat gradient buffer).
+    """Weight gradient [R][Cg_out][4][4] fp32 (force = optional {tile config, splits}), written into ``out`` when
+    given (e.g. a view of a flat gradient buffer).  The library's route (_wgrad_route) names the kernel, and with it
+    the entry point: stc_conv_wgrad_rows, stc_conv_pad_wgrad (reflect) or stc_conv_wgrad_ex.
     rows: the number of nonzero (real) channels of D when the rest is padding -- a stride-1 layer with
-    1-2 of them goes to stc_conv_wgrad_rows (which then writes only R = ``rows`` rows when R == rows).
-    pad=L.PAD_REFLECT (a Conv2d's weight gradient: Dv its output gradient, Gv its input): stc_conv_pad_wgrad, the
-    register-staged kernel with the reflect gather; no prologue, no rows kernel."""
+    1-2 of them goes to the rows kernels (which then write only R = ``rows`` rows when R == rows).
+    pad=L.PAD_REFLECT (a Conv2d's weight gradient: Dv its output gradient, Gv its input): the register-staged kernel
+    with the reflect gather; no prologue, no rows kernel."""
     l = lib()
-    if pad != L.PAD_ZEROS:
-        if dpro is not None or gpro is not None or dslope is not None or gslope is not None:
-            raise ValueError("stcgan_amd: a reflect weight gradient takes no prologue")
-        if out is not None and out.shape[0] != R:  # real rows of a padded R: through a scratch
-            full = wgrad(B, stride, Dv, R, Gv, Cg, Cg_out, dt, device=device, force=force, pad=pad)
-            out.copy_(full[:out.shape[0]])
-            return out
-        nbytes, _ = wgrad_pad_query(stride, B, Dv.H, Dv.W, R, Cg, dt, pad, force)
-        ws, nb = _ws(nbytes, device)
-        dW = _out_w(out, R, Cg_out, device)
-        fp = (ctypes.c_int32 * 2)(*force) if force is not None else None
-        check(l.stc_conv_pad_wgrad(L.dtype_code(dt), L.CONV_S2 if stride == 2 else L.CONV_S1, pad, B, Dv, R, Gv, Cg,
-                                   Cg_out, ptr(dW), fp, ptr(ws), nb, stream()), "stc_conv_pad_wgrad")
-        return dW
-    if (rows is not None and rows <= 2 and stride == 1 and (_ROWS_DEFAULT if rows_kernel is None else rows_kernel) and dpro is None and gpro is None and dslope is None
-            and gslope is None and force is None and Cg % 64 == 0 and ((Dv.H + 4) * (Dv.W + 4) + 16384) * rows <= 40000):
-        nbytes = l.stc_conv_wgrad_rows_workspace(B, Gv.H, rows, Cg)
-        ws, nb = _ws(nbytes, device)
-        if out is not None and out.shape[0] == rows:  # only the real rows (e.g. straight into a gradient view)
-            R = rows
-        dW = _out_w(out, R, Cg_out, device)
-        timer = _timer
-        if timer is not None:
-            e0, e1 = _main_events()
-        rc = l.stc_conv_wgrad_rows(L.dtype_code(dt), B, Dv, R, rows, Gv, Cg, Cg_out, ptr(dW), ptr(ws), nb, stream())
-        if timer is not None:
-            _disarm()
-        check(rc, "stc_conv_wgrad_rows")
-        if timer is not None:
-            timer.append(("wgrad_rows_kernel", True, 2.0 * B * Dv.H * Dv.W * R * 16 * Cg, e0, e1,
-                          f"wgrad s1 P={B * Dv.H * Dv.W} R{R} (real {rows}) Cg{Cg}"))
-        return dW
+    reflect = pad != L.PAD_ZEROS
+    pro = dpro is not None or gpro is not None or dslope is not None or gslope is not None
+    if reflect and pro:
+        raise ValueError("stcgan_amd: a reflect weight gradient takes no prologue")
+    if not rows or not (_ROWS_DEFAULT if rows_kernel is None else rows_kernel):
+        rows = 0
+    route = _wgrad_route(B, stride, Dv, R, Gv, Cg, Cg_out, dt, rows, pro, pad, force)
+    is_rows = route[2] in (L.WG_ROWS, L.WG_ROWS_MFMA)
+    if is_rows and out is not None and out.shape[0] == rows:  # only the real rows (e.g. straight into a gradient view)
+        R = rows
     if out is not None and out.shape[0] != R:  # real rows of a padded R: through a scratch
-        full = wgrad(B, stride, Dv, R, Gv, Cg, Cg_out, dt, dpro, dslope, gpro, gslope, device, force)
+        full = wgrad(B, stride, Dv, R, Gv, Cg, Cg_out, dt, dpro, dslope, gpro, gslope, device, force, pad=pad)
         out.copy_(full[:out.shape[0]])
         return out
-    if force is None and FORCE_WGRAD:
+    if force is None and FORCE_WGRAD and not is_rows and not reflect:
         force = FORCE_WGRAD.get((B, Dv.H, Dv.W, R, Cg))
-    nbytes, plan = wgrad_query(B, Dv.H, Dv.W, R, Cg, dt, force)
+        if force is not None:
+            route = _wgrad_route(B, stride, Dv, R, Gv, Cg, Cg_out, dt, rows, pro, pad, force)
+    nbytes, plan, _, _, name = route
+    if not is_rows and not reflect:  # the D grid's bound, whatever the stride: the cached workspace grows once per grid
+        nbytes = wgrad_query(B, Dv.H, Dv.W, R, Cg, dt, force)[0]
     ws, nb = _ws(nbytes, device)
     dW = _out_w(out, R, Cg_out, device)
-    dsc, dsh = _pro(dpro)
-    gsc, gsh = _pro(gpro)
     fp = (ctypes.c_int32 * 2)(*force) if force is not None else None
     timer, ctimer = _timer, _call_timer
     if timer is not None:
@@ -673,23 +646,31 @@ def wgrad(B, stride, Dv, R, Gv, Cg, Cg_out, dt, dpro=None, dslope=None, gpro=Non
     if ctimer is not None:
         c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         c0.record()
-    rc = l.stc_conv_wgrad_ex(L.dtype_code(dt), B, stride, Dv, R, dsc, dsh, 0 if dslope is None else 1,
-                             0.0 if dslope is None else float(dslope), Gv, Cg, Cg_out, gsc, gsh,
-                             0 if gslope is None else 1, 0.0 if gslope is None else float(gslope), ptr(dW), fp,
-                             ptr(ws), nb, stream())
+    if is_rows:
+        what = "stc_conv_wgrad_rows"
+        rc = l.stc_conv_wgrad_rows(L.dtype_code(dt), B, Dv, R, rows, Gv, Cg, Cg_out, ptr(dW), ptr(ws), nb, stream())
+    elif reflect:
+        what = "stc_conv_pad_wgrad"
+        rc = l.stc_conv_pad_wgrad(L.dtype_code(dt), L.CONV_S2 if stride == 2 else L.CONV_S1, pad, B, Dv, R, Gv, Cg,
+                                  Cg_out, ptr(dW), fp, ptr(ws), nb, stream())
+    else:
+        what = "stc_conv_wgrad_ex"
+        dsc, dsh = _pro(dpro)
+        gsc, gsh = _pro(gpro)
+        rc = l.stc_conv_wgrad_ex(L.dtype_code(dt), B, stride, Dv, R, dsc, dsh, 0 if dslope is None else 1,
+                                 0.0 if dslope is None else float(dslope), Gv, Cg, Cg_out, gsc, gsh,
+                                 0 if gslope is None else 1, 0.0 if gslope is None else float(gslope), ptr(dW), fp,
+                                 ptr(ws), nb, stream())
     if ctimer is not None:
         c1.record()
     if timer is not None:
         _disarm()
-    check(rc, "stc_conv_wgrad_ex")
-    if timer is not None or ctimer is not None:
-        dma = dt == torch.bfloat16 and dpro is None and gpro is None and dslope is None and gslope is None
-        name = _wgrad_kernel_name(plan, Dv.H, Dv.W) if dma else "wgrad_kernel"
+    check(rc, what)
     if ctimer is not None:
         ctimer.append((name, c0, c1))
     if timer is not None:
-        timer.append((name, not plan[4], 2.0 * B * Dv.H * Dv.W * R * 16 * Cg, e0, e1,
-                      f"wgrad s{stride} P={B * Dv.H * Dv.W} R{R} Cg{Cg}"))
+        timer.append((name, is_rows or not plan[4], 2.0 * B * Dv.H * Dv.W * R * 16 * Cg, e0, e1,
+                      f"wgrad s{stride} P={B * Dv.H * Dv.W} R{R}" + (f" (real {rows})" if is_rows else "") + f" Cg{Cg}"))
     return dW
 
 
